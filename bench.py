@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — VAE training throughput of the hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one optimiser step of the reference's train loop body (vae_scripts/train_vae.py:380-445:
 zero_grad, forward encode+sample+decode, L1 recon + 1e-3*KL, backward, gradient all-reduce, Adam) on one
@@ -11,7 +11,11 @@ omitted: unavailable offline / inactive before epoch 6 — state
 Inputs are resident in HBM before the timed region.  For N>1 launch with
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...``.
 
-Prints ONE JSON line (rank 0), kept under 4 KB (the driver keeps ~8 KB of stdout): metric/value/unit/..., plus
+Prints ONE JSON line (rank 0), kept under 4 KB (a reader may keep only ~8 KB of stdout): metric/value/unit/..., ms_per_step
+(wall time of one timed step).  A plain run does only what that line needs: set-up, warm-up, the timed steps and, with
+--dump-outputs DIR, what the last timed step handed back (losses, parameters, gradients) as DIR/<name>.npy.  --full adds
+the measurements that take steps or work of their own:
+  "host_enqueue_ms_per_step": host time to issue one step, from 4 extra steps with the steps-in-flight cap lifted.
   "roofline":     the dominant kernel FUNCTION by time (template instantiations folded: conv_mfma2_kernel), timed with
                   events on the launch stream during extra instrumented steps right after the timed region (so the
                   headline number is not perturbed); achieved = algorithmic FLOP (or bytes) of its launches / their
@@ -19,14 +23,15 @@ Prints ONE JSON line (rank 0), kept under 4 KB (the driver keeps ~8 KB of stdout
                   stated against it); its HBM-side fraction and the time-weighted mixed fraction ride along, and the
                   next kernels by time are listed in "secondary".
   "cpu_baseline": the CPU fp32 oracle's training step (oracle/, kind "port") on the host cores.
-The per-shape table and the per-instantiation table go to a FILE (--detail-out, default gpurun_out/r03_per_shape.json;
-copied to profiles/ when it is to be judged), not into the line.
+The per-shape table and the per-instantiation table go to a FILE (--detail-out, default bench_out/per_shape.json;
+copied to profiles/ when it is to be judged), not into the line.  Both need --full.
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -236,6 +241,35 @@ def write_detail(path, line, detail):
         return f"not written ({e})"
 
 
+DUMP_ARRAY_MAX = 6 << 20      # elements: a larger array goes out as a fixed sample of this many
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def host_outputs(tensors):
+    """{name: tensor} the last timed step handed back -> {name: float32 (float64 for integers) numpy array}.  An array of
+    more than DUMP_ARRAY_MAX elements is flattened and sampled at seeded positions, the same ones in every run."""
+    out = {}
+    for name, t in tensors.items():
+        t = t.detach().to("cpu")
+        t = t.to(torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64)
+        if t.numel() > DUMP_ARRAY_MAX:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(1234))[:DUMP_ARRAY_MAX]
+            t = t.reshape(-1)[idx.sort().values]
+        out[name] = t.numpy()
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, at most DUMP_BUDGET_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"bench.py: outputs of {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte dump budget")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 DTYPE_RAN = {"fp16": "fp16 forward operands + activations / bf16 backward operands + gradients, fp32 accumulate",
              "bf16": "bf16 operands + activations + gradients, fp32 accumulate"}
 
@@ -274,7 +308,8 @@ def bench_regression(args, cfg, dev, world, rank, dist):
 
     def step():
         opt.zero_grad()
-        loss = loss_fn(model(images), y)
+        pred = model(images)
+        loss = loss_fn(pred, y)
         loss.backward()
         if world > 1:
             flat = torch.cat([p.grad.flatten() for p in head_params])
@@ -284,7 +319,7 @@ def bench_regression(args, cfg, dev, world, rank, dist):
                 p.grad.copy_(flat[o:o + p.numel()].view_as(p) / world)
                 o += p.numel()
         opt.step()
-        return loss
+        return loss, pred
 
     def sync_all():
         if world > 1:
@@ -296,22 +331,28 @@ def bench_regression(args, cfg, dev, world, rank, dist):
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, pred = step()
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, host_outputs({
+            "loss": loss, "predictions": pred, "head_params": torch.cat([p.detach().flatten() for p in head_params]),
+            "head_grads": torch.cat([p.grad.flatten() for p in head_params])}))
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         d.all_reduce(t, op=d.ReduceOp.MAX)
         dt = float(t.item())
-    roofline = None
+    roofline = detail = None
+    if args.full:
+        if rank == 0:
+            ops.KERNEL_PROFILE = []
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            rec, ops.KERNEL_PROFILE = ops.KERNEL_PROFILE, None
+            roofline, detail = roofline_from_profile(rec, 2)
     if rank == 0:
-        ops.KERNEL_PROFILE = []
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    if rank == 0:
-        rec, ops.KERNEL_PROFILE = ops.KERNEL_PROFILE, None
-        roofline, detail = roofline_from_profile(rec, 2)
         enc_gflop = 17.66 * (size / 256.0) ** 2 if tuple(cfg_def["channels"]) == (32, 64, 128, 128) else None
         value = args.batch * world * args.steps / dt
         line = {"metric": "vae_encoder_regression_images_per_sec_256x256", "value": round(value, 2), "unit": "images/s",
@@ -324,8 +365,10 @@ def bench_regression(args, cfg, dev, world, rank, dist):
                            "global_batch": args.batch * world, "parallelism": f"dp{world}", "final_loss": round(float(loss.item()), 5)},
                 "model_tflops_per_gpu": round(value / world * enc_gflop / 1e3, 1) if enc_gflop else None,
                 "frac_of_mfma_peak_end_to_end": round(value / world * enc_gflop / 1e3 / PEAK_BF16_TFLOPS, 4) if enc_gflop else None,
-                "roofline": roofline, "env_overrides": L.env_overrides()}
-        line["detail_file"] = write_detail(args.detail_out, line, detail)
+                "env_overrides": L.env_overrides()}
+        if args.full:
+            line["roofline"] = roofline
+            line["detail_file"] = write_detail(args.detail_out, line, detail)
         print(json.dumps(line), flush=True)
     if world > 1:
         d.destroy_process_group()
@@ -339,7 +382,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--config", default=os.path.join(ROOT, "config", "vae_dente_no_adv.json"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the cpu_baseline leg")
     ap.add_argument("--perceptual", action="store_true",
                     help="add the config's perceptual_weight * LPIPS(SqueezeNet-1.1) term (models/perceptual.py, torch ops on "
                          "the device; RANDOM-INIT weights: the pretrained files cannot be fetched -- same arithmetic and cost)")
@@ -349,10 +392,15 @@ def main():
     ap.add_argument("--channels", type=int, default=None,
                     help="override the config's image channels (in = out): 3 = north_star's 'synthetic 256x256x3' variant "
                          "(+0.3 %% FLOPs: only conv_in / conv_out change; config value is 1)")
-    ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "r03_per_shape.json"),
-                    help="file for the per-shape / per-instantiation tables of the instrumented steps")
+    ap.add_argument("--detail-out", default=os.path.join(ROOT, "bench_out", "per_shape.json"),
+                    help="(--full) file for the per-shape / per-instantiation tables of the instrumented steps")
     ap.add_argument("--cpu-steps", type=int, default=10,
-                    help="timed oracle steps of the cpu_baseline leg (batch 4: ~10 s of CPU work on 16 cores)")
+                    help="(--full) timed oracle steps of the cpu_baseline leg (batch 4: ~10 s of CPU work on 16 cores)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed back (losses, parameters, gradients) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: host enqueue time, per-kernel roofline and "
+                         "per-shape tables (instrumented steps), counter-file HBM figures, the CPU baseline")
     args = ap.parse_args()
 
     import torch.distributed as dist
@@ -388,6 +436,7 @@ def main():
         cfg_def = dict(cfg_def, in_channels=args.channels, out_channels=args.channels)
     tr = cfg["autoencoder_train"]
     torch.manual_seed(42)                       # set_determinism(args.seed), train_vae.py:808
+    random.seed(42)                             # AR-VAE pairwise="subset" draws its pairs with `random`
     model = VAEModel.from_config(cfg_def).to(dev)
     # AR-VAE configs (ar_vae_dente_kl1e3.json): the attribute-regularisation term is part of the step; attributes are
     # U(0,1) per sample for the mapped names
@@ -444,45 +493,54 @@ def main():
     dt = time.perf_counter() - t0
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))   # ms, GPU-side step-to-step
     pct = lambda q: per_step[min(len(per_step) - 1, int(q * len(per_step)))]
-    # pure host enqueue time of a step: a few steps issued with the steps-in-flight cap lifted and no sync in between
-    # (the host runs ahead of the GPU; in the timed region above `host` also contains the waits on that cap)
-    cap, trainer.max_steps_in_flight = trainer.max_steps_in_flight, 1 << 20
-    h0 = time.perf_counter()
-    for _ in range(4):
-        trainer.step(images, attributes=attrs, **step_kw)
-    host_only = (time.perf_counter() - h0) / 4
-    sync_all()
-    trainer.max_steps_in_flight = cap
+    if args.dump_outputs and rank == 0:
+        # what the caller of the step receives (the loss dict) and the model it updated, before any step below
+        dump = dict(out, params=model.autoencoder.param_arena, grads=model.autoencoder.grad_arena)
+        if disc is not None:
+            dump.update(disc_params=disc.param_arena, disc_grads=disc.grad_arena)
+        write_outputs(args.dump_outputs, host_outputs(dump))
+    host_only = None
+    if args.full:
+        # pure host enqueue time of a step: a few steps issued with the steps-in-flight cap lifted and no sync in between
+        # (the host runs ahead of the GPU; in the timed region above `host` also contains the waits on that cap)
+        cap, trainer.max_steps_in_flight = trainer.max_steps_in_flight, 1 << 20
+        h0 = time.perf_counter()
+        for _ in range(4):
+            trainer.step(images, attributes=attrs, **step_kw)
+        host_only = (time.perf_counter() - h0) / 4
+        sync_all()
+        trainer.max_steps_in_flight = cap
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss = float(out["loss"].item())
-    log(f"timed region {dt:.3f}s, loss {loss:.5f}; instrumented steps")
+    log(f"timed region {dt:.3f}s, loss {loss:.5f}" + ("; instrumented steps" if args.full else ""))
 
-    # ---- instrumented steps: per-launch event timing of the MFMA conv + weight-gradient kernels (rank 0) ----
     roofline, detail = None, {}
-    if rank == 0:
-        ops.KERNEL_PROFILE = []
-    # per-kernel durations are taken with the weight gradients back on the main stream: in the timed region they
-    # run on a side stream, overlapped with the data-gradient chain, which would stretch every launch they share
-    # the GPU with (the headline number above is measured WITH the overlap)
-    side = trainer.eng.wgrad_stream
-    trainer.eng.wgrad_stream = None
-    # EVERY rank steps (the step contains collectives) and every rank takes the EAGER path: only rank 0 records, and the
-    # graph step mode would otherwise stay on for the other ranks, whose region-sized buckets do not match the eager
-    # callbacks' buckets (a collective mismatch: gloo aborts, RCCL hangs)
-    graph_mode, trainer.step_graph = trainer.step_graph, False
-    for _ in range(2):
-        trainer.step(images, attributes=attrs, **step_kw)
-    torch.cuda.synchronize()
-    trainer.step_graph = graph_mode
-    trainer.eng.wgrad_stream = side
-    if rank == 0:
-        rec, ops.KERNEL_PROFILE = ops.KERNEL_PROFILE, None
-        roofline, detail = roofline_from_profile(rec, 2)
-    if world > 1:
-        dist.barrier()
+    if args.full:
+        # ---- instrumented steps: per-launch event timing of the MFMA conv + weight-gradient kernels (rank 0) ----
+        if rank == 0:
+            ops.KERNEL_PROFILE = []
+        # per-kernel durations are taken with the weight gradients back on the main stream: in the timed region they
+        # run on a side stream, overlapped with the data-gradient chain, which would stretch every launch they share
+        # the GPU with (the headline number above is measured WITH the overlap)
+        side = trainer.eng.wgrad_stream
+        trainer.eng.wgrad_stream = None
+        # EVERY rank steps (the step contains collectives) and every rank takes the EAGER path: only rank 0 records, and the
+        # graph step mode would otherwise stay on for the other ranks, whose region-sized buckets do not match the eager
+        # callbacks' buckets (a collective mismatch: gloo aborts, RCCL hangs)
+        graph_mode, trainer.step_graph = trainer.step_graph, False
+        for _ in range(2):
+            trainer.step(images, attributes=attrs, **step_kw)
+        torch.cuda.synchronize()
+        trainer.step_graph = graph_mode
+        trainer.eng.wgrad_stream = side
+        if rank == 0:
+            rec, ops.KERNEL_PROFILE = ops.KERNEL_PROFILE, None
+            roofline, detail = roofline_from_profile(rec, 2)
+        if world > 1:
+            dist.barrier()
 
     if rank == 0:
         # algorithmic GFLOP per image and training step at 256x256 (BASELINE.md §3 / SURVEY.md §8d)
@@ -510,19 +568,21 @@ def main():
             "model_tflops_per_gpu": round(per_gpu * gflop_img / 1e3, 1) if gflop_img else None,
             "frac_of_mfma_peak_end_to_end": round(per_gpu * gflop_img / 1e3 / PEAK_BF16_TFLOPS, 4) if gflop_img else None,
             "step_ms_median": round(pct(0.5), 3), "step_ms_p10": round(pct(0.1), 3), "step_ms_p90": round(pct(0.9), 3),
-            "host_enqueue_ms_per_step": round(host_only * 1e3, 3),
             "host_in_step_call_ms_per_step": round(host / args.steps * 1e3, 3),
-            "roofline": roofline, "env_overrides": L.env_overrides(),
+            "env_overrides": L.env_overrides(),
         }
-        pmc = _pmc()
-        if pmc and "bytes_per_step" in pmc:   # HBM-side bytes of a whole step (all kernels) from the committed counter passes
-            line["end_to_end_hbm_bytes_per_step"] = pmc["bytes_per_step"]
-            line["end_to_end_hbm_frac"] = round(pmc["bytes_per_step"] / (dt / args.steps) / (PEAK_HBM_GBS * 1e9), 4)
-            line["end_to_end_hbm_source"] = f"profiles/{PMC_TRAFFIC_FILE}"
-        if world == 1 and not args.no_cpu_baseline:
-            log("cpu baseline (oracle) ...")
-            line["cpu_baseline"] = cpu_baseline(cfg_def, args.size, 4, args.cpu_steps)
-        line["detail_file"] = write_detail(args.detail_out, line, detail)
+        if args.full:
+            line["host_enqueue_ms_per_step"] = round(host_only * 1e3, 3)
+            line["roofline"] = roofline
+            pmc = _pmc()
+            if pmc and "bytes_per_step" in pmc:   # HBM-side bytes of a whole step (all kernels) from the committed counter passes
+                line["end_to_end_hbm_bytes_per_step"] = pmc["bytes_per_step"]
+                line["end_to_end_hbm_frac"] = round(pmc["bytes_per_step"] / (dt / args.steps) / (PEAK_HBM_GBS * 1e9), 4)
+                line["end_to_end_hbm_source"] = f"profiles/{PMC_TRAFFIC_FILE}"
+            if world == 1 and not args.no_cpu_baseline:
+                log("cpu baseline (oracle) ...")
+                line["cpu_baseline"] = cpu_baseline(cfg_def, args.size, 4, args.cpu_steps)
+            line["detail_file"] = write_detail(args.detail_out, line, detail)
         out_line = json.dumps(line)
         if len(out_line) >= 4096:      # the driver keeps ~8 KB of stdout: never let the line outgrow it again
             line["roofline"].pop("secondary", None)

@@ -22,7 +22,7 @@ def main():
     env = dict(os.environ, PTI_DIST_BACKEND="gloo", PTI_SHARE_GPU="1")
     with open(os.path.join(outdir, "bench_dp2.out"), "w") as out, open(os.path.join(outdir, "bench_dp2.err"), "w") as err:
         rc = subprocess.run(run + ["--master-port", p2, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "3",
-                                   "--batch", "2", "--size", "64", "--no-cpu-baseline", "--detail-out", os.path.join(outdir, "bench_dp2_detail.json")],
+                                   "--batch", "2", "--size", "64", "--full", "--no-cpu-baseline", "--detail-out", os.path.join(outdir, "bench_dp2_detail.json")],
                             cwd=ROOT, env=env, stdout=out, stderr=err).returncode
     with open(os.path.join(outdir, "bench_dp2.rc"), "w") as f:
         f.write(str(rc))

@@ -3,7 +3,7 @@
 root=$PWD
 out=/tmp/prof_variant; rm -rf $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $out --output-format csv -- python3 "$root/bench.py" --steps 6 --warmup 3 --no-cpu-baseline "$@" > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $out --output-format csv -- python3 "$root/bench.py" --full --steps 6 --warmup 3 --no-cpu-baseline "$@" > /dev/null 2>&1
 f=$(find $out -name '*kernel_stats.csv' | head -1)
 python3 - "$f" <<'PY'
 import csv, sys
