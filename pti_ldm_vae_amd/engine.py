@@ -14,6 +14,8 @@ flat gradient arena and hand autograd views of it.
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 
 import torch
@@ -35,6 +37,23 @@ class _Act:
 
 def _empty(shape, like, dtype=BF16):
     return torch.empty(shape, dtype=dtype, device=like.device)
+
+
+@contextlib.contextmanager
+def gc_off_for_capture():
+    """Around a HIP-graph capture: collect the garbage first and keep the cyclic collector off until the capture is over.
+    A dropped model is cyclic garbage (its engine and its net reference each other), and the collector may otherwise
+    finalise it in the middle of a capture, destroying the HIP graphs and graph-pool tensors it holds while a stream is
+    capturing.  In the test suite a collection inside a training-step capture aborted the process, with a dropped
+    engine's captured inference graphs pending collection.  torch.cuda.graph no longer collects on entry by default."""
+    gc.collect()
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 # =================================================================================================
@@ -160,11 +179,11 @@ class _MfmaConv:
             eng.defer_wgrad(x.t, dy, dw, db)     # launched with other layers' weight gradients (Engine.flush_wgrad)
             return
         g, b = (norm.weight.data, norm.bias.data) if norm is not None else (None, None)
+        kw = dict(ksize=self.ksize, mode=self.mode, prologue=pro, in_stats=x.stats if pro else None, gamma=g, beta=b,
+                  groups=eng.G, eps=eng.eps, accumulate=True)
         ws = eng.wgrad_stream
         if ws is None:
-            ops.conv_wgrad_mfma(x.t, dy, dw, db, ksize=self.ksize, mode=self.mode, prologue=pro,
-                                in_stats=x.stats if pro else None, gamma=g, beta=b, groups=eng.G, eps=eng.eps,
-                                accumulate=True, workspace=eng.workspace)
+            ops.conv_wgrad_mfma(x.t, dy, dw, db, workspace=eng.workspace, **kw)
             return
         # weight gradients are off the data-gradient chain: they run on a side stream, behind an event that marks
         # "x and dy exist", and are joined before their gradients are used (Engine.join_wgrad)
@@ -172,12 +191,9 @@ class _MfmaConv:
         ev = torch.cuda.Event()
         ev.record(cur)
         ws.wait_event(ev)
-        x.t.record_stream(ws)
-        dy.record_stream(ws)
+        eng.record_side(x.t, dy, dw, db, *kw.values())
         with torch.cuda.stream(ws):
-            ops.conv_wgrad_mfma(x.t, dy, dw, db, ksize=self.ksize, mode=self.mode, prologue=pro,
-                                in_stats=x.stats if pro else None, gamma=g, beta=b, groups=eng.G, eps=eng.eps,
-                                accumulate=True, workspace=eng.workspace_side)
+            ops.conv_wgrad_mfma(x.t, dy, dw, db, workspace=eng.workspace_side, **kw)
         eng._wgrad_pending = True
 
 
@@ -345,6 +361,7 @@ class _DirectConv:
         # Engine sets ``img_mfma`` (it knows which two convs face the image).
         self.img_mfma = False
         self.wp_img = self.wpt_img = self.wpad_img = self.bpad_img = None
+        self.dw_img = self.db_img = None
 
     def alloc(self):
         """Buffers of the derived operands, allocated ONCE: captured HIP graphs (inference encode / decode, the training
@@ -363,6 +380,14 @@ class _DirectConv:
             shape = (self.cout, 32, 3, 3) if self.cin < self.cout else (32, self.cin, 3, 3)
             self.wpad_img = torch.zeros(shape, dtype=F32, device=w.device)
             self.bpad_img = torch.zeros(32, dtype=F32, device=w.device)
+            # the padded conv's weight (and, conv_out, bias) gradient: written by the side-stream weight-gradient launch,
+            # copied into the gradient arena by its post() on that stream.  Engine-owned rather than a per-step
+            # temporary: a temporary's block would go back to the main stream's pool once the flush dropped its
+            # post() -- while the side stream may not have run yet -- and the step's later allocations could take it
+            # (one buffer per conv instead of record_stream on every job / post operand; zeroed on the side stream,
+            # right before its launch: Engine.wgrad_padded)
+            self.dw_img = torch.zeros(shape, dtype=F32, device=w.device)
+            self.db_img = torch.zeros(32, dtype=F32, device=w.device) if self.cout < self.cin else None
 
     def repack_entries(self):
         """Entries of the one-launch re-pack (ops.DirectRepack): w -> w_tck, its tap-reversed transpose (the
@@ -428,6 +453,7 @@ class Engine:
         self.wgrad_stream = torch.cuda.Stream(device=self.dev) if os.environ.get("PTI_WGRAD_STREAM", "1") == "1" else None
         self.workspace_side = torch.empty_like(self.workspace) if self.wgrad_stream is not None else None
         self._wgrad_pending = False
+        self._side_owned = set()
         # weight gradients of the plain 3x3 convs are collected while backward walks the layers and launched a batch
         # at a time (one launch has ~11 us of fixed cost against 10-45 us of streaming per layer, and the layers'
         # weight gradients are independent): PTI_WGRAD_BATCH = jobs per launch (default 16 = the C-ABI's maximum; 1 = off).
@@ -474,7 +500,7 @@ class Engine:
         self.enc_in.img_mfma = img and 2 <= net.in_channels <= 8 and net.channels[0] % 32 == 0
         self.dec_out.img_mfma = img and 2 <= net.out_channels <= 8 and net.channels[0] % 32 == 0
         self.enc_in.pack_f16 = self.dec_out.pack_f16 = self.act_dtype == torch.float16
-        self._wgrad_posts = []
+        self._wgrad_posts, self._wgrad_zero = [], ()
         self._flush_up = int(os.environ.get("PTI_WGRAD_FLUSH_UP", "1"))
         # GroupNorm backward of a ResBlock's second norm applied inside the first conv's data-gradient launch (128-wide
         # tiles; csrc/conv_mfma.hip PRO_GNB) instead of a pti_gn_bwd_apply pass.  OFF by default (PTI_GNBWD_CHAIN=1): built
@@ -522,6 +548,9 @@ class Engine:
         cmax = max(self.net.channels)
         self._zpool_size = (64 * batch * cmax * 2) if backward else (96 * batch * self.G * 2)
         self._zpool = None
+        if backward and self.wgrad_stream is not None:    # (record_side: buffers that outlive every launch)
+            self._side_owned = {t.untyped_storage().data_ptr()
+                                for t in (self.net.param_arena, self.net.grad_arena, self.workspace_side)}
 
     def _pack_buffer_ids(self):
         """Addresses of every derived weight operand a captured inference graph reads."""
@@ -610,11 +639,23 @@ class Engine:
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         ws.wait_event(ev)
-        wide.record_stream(ws)
-        narrow.record_stream(ws)
+        self.record_side(wide, narrow, *args, *kw.values())
         with torch.cuda.stream(ws):
             ops.wgrad_direct(wide, narrow, *args, workspace=self.workspace_side, **kw)
         self._wgrad_pending = True
+
+    def record_side(self, *operands):
+        """``record_stream(wgrad_stream)`` on every tensor among ``operands`` (the operands of a side-stream launch) that
+        is not a view of an engine-owned buffer (parameter / gradient arena, side workspace): the caching allocator then
+        keeps a temporary's block out of circulation until the side stream has passed this point, however early the
+        main stream drops its last reference.  The forward pass's GroupNorm statistics (``in_stats`` of the prologue
+        weight gradients), for one, are views of a per-pass scratch pool that nothing holds once the pass's context is
+        gone -- in the captured training step that is before the side stream has read them."""
+        ws = self.wgrad_stream
+        owned = self._side_owned
+        for t in operands:
+            if isinstance(t, torch.Tensor) and t.untyped_storage().data_ptr() not in owned:
+                t.record_stream(ws)
 
     def side_call(self, fn, *tensors):
         """Run ``fn`` (small launches that only the optimiser step waits for) on the weight-gradient stream, behind
@@ -632,9 +673,10 @@ class Engine:
             fn()
         self._wgrad_pending = True
 
-    def defer_wgrad(self, x, dy, dw, db, post=None):
+    def defer_wgrad(self, x, dy, dw, db, post=None, zero=()):
         """``post``: called right behind the batched launch, on its stream (the image-side convs copy the real rows /
-        columns of their zero-padded weight gradient into the gradient arena there)."""
+        columns of their zero-padded weight gradient into the gradient arena there); ``zero``: buffers cleared on that
+        stream right before the launch (the image-side convs' padded gradients)."""
         # The encoder's backward climbs from the smallest maps to the largest: the jobs still queued from the level below are
         # launched when the first job of a LARGER level arrives, instead of waiting for the batch to fill or for the
         # optimiser's join -- without this the final flush carried 128- and 64-channel jobs that had been ready for a
@@ -648,26 +690,32 @@ class Engine:
         self._wgrad_jobs.append((x, dy, dw, db))
         if post is not None:
             self._wgrad_posts.append(post)
+        self._wgrad_zero += zero
         if len(self._wgrad_jobs) >= self.wgrad_batch_max:
             self.flush_wgrad()
 
-    def wgrad_padded(self, x, dy, dw, db, post):
+    def wgrad_padded(self, x, dy, dw, db, post, zero):
         """Weight gradient of an image-side conv on its zero-padded 32-channel operands (same protocol as
-        _MfmaConv.wgrad: batched and on the side stream when those are on)."""
+        _MfmaConv.wgrad: batched and on the side stream when those are on).  ``zero``: the engine-owned buffers among
+        dw / db (_DirectConv.dw_img / db_img) -- cleared on the launch's stream right before it, so that on the in-order
+        side stream the clear also follows the previous step's ``post``."""
         if self.batch_wgrad and ops.wgrad_batch_eligible(x, dy, 3, PTI_CONV_S1, PTI_PRO_NONE):
-            self.defer_wgrad(x, dy, dw, db, post)
+            self.defer_wgrad(x, dy, dw, db, post, zero)
             return
         ws = self.wgrad_stream
         if ws is None:
+            for t in zero:
+                t.zero_()
             ops.conv_wgrad_mfma(x, dy, dw, db, accumulate=True, workspace=self.workspace)
             post()
             return
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         ws.wait_event(ev)
-        x.record_stream(ws)
-        dy.record_stream(ws)
+        self.record_side(x, dy, dw, db)
         with torch.cuda.stream(ws):
+            for t in zero:
+                t.zero_()
             ops.conv_wgrad_mfma(x, dy, dw, db, accumulate=True, workspace=self.workspace_side)
             post()
         self._wgrad_pending = True
@@ -677,9 +725,12 @@ class Engine:
         ranges to the exchange -- in their original order, behind that launch."""
         jobs, self._wgrad_jobs = self._wgrad_jobs, []
         posts, self._wgrad_posts = self._wgrad_posts, []
+        zero, self._wgrad_zero = self._wgrad_zero, ()
         ws = self.wgrad_stream
         if jobs:
             if ws is None:
+                for t in zero:
+                    t.zero_()
                 ops.conv_wgrad_mfma_batched(jobs, workspace=self.workspace)
                 for p in posts:
                     p()
@@ -687,10 +738,11 @@ class Engine:
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream())
                 ws.wait_event(ev)
-                for x, dy, _, _ in jobs:
-                    x.record_stream(ws)
-                    dy.record_stream(ws)
+                for job in jobs:
+                    self.record_side(*job)
                 with torch.cuda.stream(ws):
+                    for t in zero:
+                        t.zero_()
                     ops.conv_wgrad_mfma_batched(jobs, workspace=self.workspace_side)
                     for p in posts:
                         p()
@@ -830,10 +882,10 @@ class Engine:
         _, cin, h, w = x.shape
         c0 = dout.shape[3]
         if ei.img_mfma:   # x = the saved zero-padded image (bf16): dW[c0][32 (pad)] -> its first cin columns
-            dwp = torch.zeros(c0, 32, 3, 3, dtype=F32, device=x.device)
+            dwp = ei.dw_img
             gw = gv(ei.prefix + ".weight")
             self.wgrad_padded(xpad_b, dout, dwp, gv(ei.prefix + ".bias"),
-                              lambda: gw.view(c0, cin, 3, 3).add_(dwp[:, :cin]))
+                              lambda: gw.view(c0, cin, 3, 3).add_(dwp[:, :cin]), (dwp,))
         else:
             self._wgrad_direct(dout, x, gv(ei.prefix + ".weight"), n=n, h=h, w=w, cw=c0, cn=cin, ksize=3, sgn=-1,
                                narrow_layout="nchw", dw_strides=(1, cin * 9, 9), dbias_wide=gv(ei.prefix + ".bias"))
@@ -891,14 +943,13 @@ class Engine:
         da = _empty(act.t.shape, z)
         if do.img_mfma:   # d recon zero-padded to 32 channels (bf16): weight gradient dW[32 (pad)][C] -> its first co rows
             dpad, _ = ops.pad_nchw_to_nhwc32(drecon, BF16)
-            dwp = torch.zeros(32, C, 3, 3, dtype=F32, device=z.device)
-            dbp = torch.zeros(32, dtype=F32, device=z.device)
+            dwp, dbp = do.dw_img, do.db_img
             gw, gb = gv(do.prefix + ".weight"), gv(do.prefix + ".bias")
 
             def post():
                 gw.view(co, C, 3, 3).add_(dwp[:co])
                 gb.add_(dbp[:co])
-            self.wgrad_padded(gact, dpad, dwp, dbp, post)
+            self.wgrad_padded(gact, dpad, dwp, dbp, post, (dwp, dbp))
             ops.conv_mfma(dpad, do.wpt_img, None, da, cout=C, ksize=3)
         else:
             self._wgrad_direct(act.t, drecon, gv(do.prefix + ".weight"), n=n, h=h, w=w, cw=C, cn=co, ksize=3, sgn=1,
@@ -970,7 +1021,8 @@ class Engine:
             cur.wait_stream(side)
             g = torch.cuda.CUDAGraph()
             try:
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):   # loader threads may issue copies meanwhile
+                # (thread_local: loader threads may issue copies meanwhile)
+                with gc_off_for_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
                     mu, sigma, _ = self.encode_forward(sx, save=False)
             except Exception as ex:   # eager from here on
                 import warnings
@@ -1016,7 +1068,8 @@ class Engine:
             cur.wait_stream(side)
             g = torch.cuda.CUDAGraph()
             try:
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):   # loader threads may issue copies meanwhile
+                # (thread_local: loader threads may issue copies meanwhile)
+                with gc_off_for_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
                     recon, _ = self.decode_forward(sz, save=False)
             except Exception as ex:   # eager from here on
                 import warnings

@@ -27,6 +27,7 @@ import torch
 
 from . import ops
 from .data_parallel import FlatGradAllReducer, broadcast_parameters
+from .engine import gc_off_for_capture
 from .optim import FlatAdam
 
 
@@ -337,7 +338,8 @@ class VAETrainer:
             # last packed eagerly.  Force the dirty state for the capture.
             self.eng.packed_version = -1
             try:
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):   # loader threads may issue copies meanwhile
+                # (thread_local: loader threads may issue copies meanwhile)
+                with gc_off_for_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
                     out2 = self._plain_fwd_bwd(gx, geps)
             except Exception as ex:   # a capture that fails must not take the run down: eager from here on
                 import warnings
@@ -382,10 +384,11 @@ class VAETrainer:
             self.eng.packed_version = -1          # the re-pack launches are part of the first graph (see _step_graphed)
             self.eng.grad_ready_cb = None
             try:
-                with torch.cuda.graph(ga, capture_error_mode="thread_local"):
-                    out2, carry = self._plain_fwd_dec_bwd(gx, geps, join=True)
-                with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
-                    self._plain_enc_bwd(carry)
+                with gc_off_for_capture():
+                    with torch.cuda.graph(ga, capture_error_mode="thread_local"):
+                        out2, carry = self._plain_fwd_dec_bwd(gx, geps, join=True)
+                    with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
+                        self._plain_enc_bwd(carry)
             except Exception as ex:
                 import warnings
                 warnings.warn(f"HIP-graph capture of the data-parallel step failed ({ex!r}); continuing with eager launches")
