@@ -29,7 +29,9 @@ extern "C" {
 typedef void* pti_stream_t; /* hipStream_t */
 
 #define PTI_ABI_VERSION 5   /* 5 (round 3): + pti_direct_repack, pti_pad_nchw_to_nhwc32 / pti_slice_nhwc32_to_nchw,
-                                 pti_conv2d_mfma_gnbwd_chain (+ _supported), pti_gn_affine_grads, pti_gn_sums_finalize_affine */
+                                 pti_conv2d_mfma_gnbwd_chain (+ _supported), pti_gn_affine_grads, pti_gn_sums_finalize_affine
+                               Still 5: pti_image_metrics / pti_image_metrics_ws_floats were APPENDED (no existing entry
+                               point, structure or constant changed), so a caller built against the earlier 5 keeps working. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -440,6 +442,24 @@ int pti_lpips_tap_nhwc_fwd(const void* a, const void* b, const float* w, float* 
                            int hw, pti_stream_t s);
 int pti_lpips_tap_nhwc_bwd(const void* a, const void* b, const float* w, const float* saved, const float* gout, void* ga,
                            int n, int c, int hw, pti_stream_t s);
+
+
+/* ---- evaluation metrics (reference vae_scripts/evaluate_vae.py:87-99, src/pti_ldm_vae/utils/eval_metrics.py:6-64) ----
+ * pred, target: fp32 NCHW [n][c][h][w] (dense).  out_n4[i] = {mse, mae, psnr, ssim} of sample i:
+ *   clamp != 0: both images are clamped to [lo, hi] as they are loaded;
+ *   mse / mae = mean over (c, h, w) of the squared / absolute difference;  psnr = 10 log10(data_range^2 / max(mse, 1e-12));
+ *   ssim = mean over (c, h, w) of the SSIM map of an 11x11 separable window with taps taps11 (HOST array of 11 floats,
+ *          copied into the launch: the Gaussian sigma 1.5 normalised to sum 1 as compute_ssim builds it), zero padding 5
+ *          without renormalisation at the border, c1 = (k1 data_range)^2, c2 = (k2 data_range)^2; each channel is filtered
+ *          on its own (the reference function only runs for c == 1).
+ * workspace: pti_image_metrics_ws_floats(n, c, h, w) floats of device scratch (per-tile partial sums, plain stores, added
+ * up in a fixed order by a second launch: no float atomics, bitwise reproducible, and a sample's result does not depend
+ * on n or on its position in the batch).  pti_image_metrics_ws_floats is pure host arithmetic; 0 = unsupported shape
+ * (any dimension < 1, or too large to index).  Any h, w >= 1 is supported.                                              */
+int64_t pti_image_metrics_ws_floats(int n, int c, int h, int w);
+int pti_image_metrics(const float* pred, const float* target, int n, int c, int h, int w, int clamp, float lo, float hi,
+                      float data_range, float k1, float k2, const float* taps11, float* out_n4, float* workspace,
+                      pti_stream_t s);
 
 #ifdef __cplusplus
 }

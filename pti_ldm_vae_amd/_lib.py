@@ -152,6 +152,8 @@ SIGNATURES = {
     "pti_preprocess_batch": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "pti_cast_nchw_f32_to_nhwc_bf16": (_I, [_P, _P, _I, _I, _I, _P]),
     "pti_cast_nhwc_bf16_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _P]),
+    "pti_image_metrics_ws_floats": (_I64, [_I, _I, _I, _I]),
+    "pti_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -221,6 +221,27 @@ def create_vae_dataloaders(data_base_dir: str, batch_size: int, patch_size: tupl
     return train, val, train_paths, val_paths
 
 
+def list_inference_paths(input_dir: str, num_samples: int | None = None) -> list[str]:
+    """The image list of ``create_vae_inference_dataloader``: ``list_tif_paths(input_dir, "both")`` (``*.tif`` directly in
+    the folder, else its ``edente`` then ``dente`` sub-folders), capped to the first ``num_samples``.  An empty folder
+    raises ``FileNotFoundError``."""
+    paths = list_tif_paths(input_dir, "both")
+    if not paths:
+        raise FileNotFoundError(f"No .tif images found in {input_dir}")
+    return paths if num_samples is None else paths[:num_samples]
+
+
+def create_vae_inference_dataloader(input_dir: str, patch_size: tuple[int, int], batch_size: int,
+                                    num_samples: int | None = None, num_workers: int = 4, device="cuda"):
+    """Same signature and return shape as the reference's ``create_vae_inference_dataloader``
+    (dataloaders.py:332-367): ``(loader, paths)`` -- one loader over the folder's images in sorted order with the
+    training pipeline's resize + masked z-score, no shuffling, no attributes, no split; the short last batch is kept.
+    The loader yields device batches ``[b, 1, Hp, Wp]`` (``DeviceImageLoader``)."""
+    paths = list_inference_paths(input_dir, num_samples)
+    loader = DeviceImageLoader(paths, batch_size, patch_size, device, shuffle=False, num_workers=num_workers)
+    return loader, paths
+
+
 def create_regression_dataloaders(data_base_dir: str, attributes_path, targets: list[str], batch_size: int,
                                   patch_size: tuple[int, int], train_split: float = 0.9, num_workers: int = 4,
                                   seed: int | None = 42, subset_size: int | None = None, val_dir: str | None = None,

@@ -756,6 +756,61 @@ def preprocess_batch(src, offsets, hw, out, stats=None):
     return out
 
 
+# ---- evaluation metrics (csrc/image_metrics.hip; include/pti_vae.h "evaluation metrics") ------------------------------
+SSIM_WINDOW, SSIM_SIGMA = 11, 1.5
+_ssim_taps = None
+_metrics_ws = {}
+
+
+def ssim_taps() -> torch.Tensor:
+    """The 11 fp32 taps of the SSIM window, built on the host the way the reference's ``compute_ssim`` builds them
+    (eval_metrics.py:37-41): fp32 ``exp`` of -(i-5)^2 / (2 sigma^2), divided by their fp32 sum."""
+    global _ssim_taps
+    if _ssim_taps is None:
+        coords = torch.arange(SSIM_WINDOW) - SSIM_WINDOW // 2
+        g = torch.exp(-(coords ** 2) / (2 * SSIM_SIGMA * SSIM_SIGMA))
+        _ssim_taps = (g / g.sum()).to(F32).contiguous()
+    return _ssim_taps
+
+
+def image_metrics(pred, target, *, clamp=None, data_range=1.0, k1=0.01, k2=0.03, out=None):
+    """Per-sample ``[mse, mae, psnr, ssim]`` of two fp32 ``[n, c, h, w]`` device batches in one fused pass
+    (``pti_image_metrics``) -> fp32 ``[n, 4]`` device tensor.
+
+    ``clamp=(lo, hi)`` clamps both inputs as they are loaded (evaluate_vae.py clamps to [0, 1] first).  PSNR and SSIM follow
+    the reference's ``compute_psnr`` / ``compute_ssim``: 11x11 Gaussian window (sigma 1.5), zero padding without border
+    renormalisation.  The reference function only runs for ``c == 1``; for ``c > 1`` the same window is applied to each
+    channel on its own (depthwise) and SSIM is the mean over all channels.  Non-contiguous or non-fp32 inputs are copied
+    to contiguous fp32 first.  Runs on the current stream, no host sync; the scratch buffer is cached per (stream, shape)."""
+    if not (pred.is_cuda and target.is_cuda):
+        raise ValueError("image_metrics: expected CUDA(HIP) tensors")
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise ValueError(f"image_metrics: expected two [n, c, h, w] tensors of one shape, got {tuple(pred.shape)} / {tuple(target.shape)}")
+    if not (pred.is_floating_point() and target.is_floating_point()):
+        raise TypeError("image_metrics: expected floating-point images")
+    pred, target = pred.to(F32).contiguous(), target.to(F32).contiguous()
+    n, c, h, w = pred.shape
+    floats = L.lib().pti_image_metrics_ws_floats(n, c, h, w)
+    if floats <= 0:
+        raise ValueError(f"image_metrics: unsupported shape {tuple(pred.shape)}")
+    if out is None:
+        out = torch.empty(n, 4, dtype=F32, device=pred.device)
+    else:
+        _chk(out, F32, "out", 2)
+        if tuple(out.shape) != (n, 4) or out.device != pred.device:
+            raise ValueError(f"image_metrics: out must be [{n}, 4] on {pred.device}")
+    stream = _stream()
+    key = (pred.device.index, stream, n, c, h, w)
+    ws = _metrics_ws.get(key)
+    if ws is None:
+        ws = _metrics_ws[key] = torch.empty(floats, dtype=F32, device=pred.device)
+    lo, hi = (0.0, 0.0) if clamp is None else (float(clamp[0]), float(clamp[1]))
+    L.check(L.lib().pti_image_metrics(_ptr(pred), _ptr(target), n, c, h, w, int(clamp is not None), lo, hi, float(data_range),
+                                      float(k1), float(k2), C.c_void_p(ssim_taps().data_ptr()), _ptr(out), _ptr(ws), stream),
+            "pti_image_metrics")
+    return out
+
+
 # ---- PatchDiscriminator passes (csrc/discriminator.hip; include/pti_vae.h "PatchDiscriminator") -----------------------
 def pd_out_hw(h, w, stride):
     return (h + 2 - 4) // stride + 1, (w + 2 - 4) // stride + 1

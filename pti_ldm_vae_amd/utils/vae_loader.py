@@ -1,6 +1,7 @@
 """Config + checkpoint -> eval-mode ``VAEModel`` (reference ``src/pti_ldm_vae/utils/vae_loader.py:27-43``)."""
 from __future__ import annotations
 
+from pathlib import Path
 from typing import Any
 
 import torch
@@ -18,3 +19,8 @@ def load_vae_model(config: Any, checkpoint_path: str, device: torch.device) -> V
     autoencoder.load_state_dict(state_dict)
     autoencoder.eval()
     return autoencoder
+
+
+def default_eval_output_dir(config_file: str, root_dir: str = "evals") -> Path:
+    """``<root_dir>/<config file name without its suffix>`` (vae_loader.py:46-57): where ``evaluate_vae`` writes by default."""
+    return Path(root_dir) / Path(config_file).stem
