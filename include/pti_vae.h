@@ -30,8 +30,9 @@ typedef void* pti_stream_t; /* hipStream_t */
 
 #define PTI_ABI_VERSION 5   /* 5 (round 3): + pti_direct_repack, pti_pad_nchw_to_nhwc32 / pti_slice_nhwc32_to_nchw,
                                  pti_conv2d_mfma_gnbwd_chain (+ _supported), pti_gn_affine_grads, pti_gn_sums_finalize_affine
-                               Still 5: pti_image_metrics / pti_image_metrics_ws_floats were APPENDED (no existing entry
-                               point, structure or constant changed), so a caller built against the earlier 5 keeps working. */
+                               Still 5: pti_image_metrics / pti_image_metrics_ws_floats, and after them pti_latent_pairwise /
+                               pti_latent_group_stats (+ their _ws_floats), were APPENDED (no existing entry point, structure
+                               or constant changed), so a caller built against the earlier 5 keeps working. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -460,6 +461,31 @@ int64_t pti_image_metrics_ws_floats(int n, int c, int h, int w);
 int pti_image_metrics(const float* pred, const float* target, int n, int c, int h, int w, int clamp, float lo, float hi,
                       float data_range, float k1, float k2, const float* taps11, float* out_n4, float* workspace,
                       pti_stream_t s);
+
+/* ---- latent-space analysis (reference src/pti_ldm_vae/analysis/latent_space.py:40-66 and :90-102; csrc/latent_stats.hip) ----
+ * All matrices are fp32, row-major with a row stride in ELEMENTS (lda, ldb >= d; ldo >= n2); accumulation is fp32 in one
+ * fixed order that depends on d only (fmaf chains over 512-column slabs, slab sums added in ascending order), no atomics:
+ * results are bitwise reproducible and entry (i, j) depends on rows i and j only.
+ *
+ * pti_latent_pairwise: out[i][j] for rows i of a [n1][d] and j of b [n2][d] (a and b may be the same pointer):
+ *   mode 0: sqrt(sum_k (a[i][k] - b[j][k])^2)   (scipy cdist, accumulated as differences);   mode 1: sum_k a[i][k] b[j][k].
+ *   center (may be NULL): d floats subtracted from both operands as they are loaded; mode 1 with the column mean is the
+ *   centred Gram matrix of PCA.
+ *   workspace: pti_latent_pairwise_ws_floats(n1, n2, d) floats (never 0 for a supported shape; used when few output
+ *   tiles meet long rows: d is then split over workgroups and a second launch folds the partial tiles in the same order).
+ * pti_latent_group_stats: rows of a / b grouped by patient; seg_a, seg_b: int32 DEVICE arrays of patients + 1 ascending
+ *   row offsets.  out_e4[p] = {|mean_a - mean_b|, mean over d of the population std of the patient's a rows (two-pass, as
+ *   np.std; 0 for a single row), the same for b, mean of all cross distances} = compute_distance_metrics of that patient.
+ *   A patient without rows on either side -- or whose offsets are not ascending or leave [0, n] -- gets four NaNs; the
+ *   kernels never read outside the matrices whatever the tables hold.  Any d >= 1.
+ *   workspace: pti_latent_group_stats_ws_floats(n1, n2, patients, d) floats, 8-byte aligned.
+ * Both *_ws_floats are pure host arithmetic; 0 = unsupported shape (a dimension < 1 or too large to index).            */
+int64_t pti_latent_pairwise_ws_floats(int n1, int n2, int d);
+int pti_latent_pairwise(const float* a, int64_t lda, int n1, const float* b, int64_t ldb, int n2, int d, const float* center,
+                        int mode, float* out, int64_t ldo, float* workspace, pti_stream_t s);
+int64_t pti_latent_group_stats_ws_floats(int n1, int n2, int patients, int d);
+int pti_latent_group_stats(const float* a, int64_t lda, int n1, const int32_t* seg_a, const float* b, int64_t ldb, int n2,
+                           const int32_t* seg_b, int patients, int d, float* out_e4, float* workspace, pti_stream_t s);
 
 #ifdef __cplusplus
 }

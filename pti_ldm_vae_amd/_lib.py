@@ -154,6 +154,10 @@ SIGNATURES = {
     "pti_cast_nhwc_bf16_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _P]),
     "pti_image_metrics_ws_floats": (_I64, [_I, _I, _I, _I]),
     "pti_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "pti_latent_pairwise_ws_floats": (_I64, [_I, _I, _I]),
+    "pti_latent_pairwise": (_I, [_P, _I64, _I, _P, _I64, _I, _I, _P, _I, _P, _I64, _P, _P]),
+    "pti_latent_group_stats_ws_floats": (_I64, [_I, _I, _I, _I]),
+    "pti_latent_group_stats": (_I, [_P, _I64, _I, _P, _P, _I64, _I, _P, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -1,0 +1,302 @@
+"""Latent-space analysis of a trained VAE (reference ``src/pti_ldm_vae/analysis/latent_space.py``: same names, signatures,
+error texts and output files).
+
+What differs is where the arithmetic runs.  The latents of all images stay on the device as one ``[N, D]`` matrix
+(D = 4 096 .. 40 960); the per-patient distance statistics of all patients come out of ONE ``ops.latent_group_stats``
+call, and PCA takes the centred Gram matrix ``Xc Xc^T`` from ``ops.latent_pairwise(mode="dot", center=mean)`` and
+diagonalises that N x N matrix in fp64 on the host.  Only results cross to the host.  t-SNE and UMAP remain host
+libraries fed with the PCA output."""
+from __future__ import annotations
+
+import os
+from glob import glob
+from pathlib import Path
+
+import numpy as np
+import torch
+
+# plotly.express.colors.qualitative.Plotly + Dark24, the palette the reference cycles through (fixed here: plotly is optional)
+PATIENT_PALETTE = (
+    "#636EFA", "#EF553B", "#00CC96", "#AB63FA", "#FFA15A", "#19D3F3", "#FF6692", "#B6E880", "#FF97FF", "#FECB52",
+    "#2E91E5", "#E15F99", "#1CA71C", "#FB0D0D", "#DA16FF", "#222A2A", "#B68100", "#750D86", "#EB663B", "#511CFB",
+    "#00A08B", "#FB00D1", "#FC0080", "#B2828D", "#6C7C32", "#778AAE", "#862A16", "#A777F1", "#620042", "#1616A7",
+    "#DA60CA", "#6C4516", "#0D2A63", "#AF0038")
+
+
+def extract_patient_id_from_filename(filename: str) -> str:
+    """``"1000_HA_2021_02_545.tif" -> "545"``: the last ``_``-separated part of the name without its extension."""
+    stem = filename.rsplit(".", 1)[0] if "." in filename else filename
+    return stem.split("_")[-1]
+
+
+def load_image_paths(data_dir: str, max_images: int | None = None, extensions: list[str] | None = None) -> list[str]:
+    """Sorted paths of the files in ``data_dir`` with one of ``extensions`` (default ``.tif`` / ``.tiff``; the leading
+    dot is optional), capped to the first ``max_images``."""
+    found: list[str] = []
+    for ext in extensions if extensions is not None else [".tif", ".tiff"]:
+        found.extend(glob(os.path.join(data_dir, f"*{ext if ext.startswith('.') else '.' + ext}")))
+    found.sort()
+    return found if max_images is None else found[:max_images]
+
+
+def _is_device_tensor(x) -> bool:
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def _host_metrics(p1: np.ndarray, p2: np.ndarray) -> tuple[float, float, float, float]:
+    """fp64 numpy: centre distance, mean population std of each side (0 for one row), mean of all cross distances."""
+    p1, p2 = np.asarray(p1, dtype=np.float64), np.asarray(p2, dtype=np.float64)
+    gap = p1.mean(axis=0) - p2.mean(axis=0)
+    center = float(np.sqrt(np.dot(gap, gap)))
+    std1 = float(p1.std(axis=0).mean()) if len(p1) > 1 else 0.0
+    std2 = float(p2.std(axis=0).mean()) if len(p2) > 1 else 0.0
+    total = 0.0
+    for row in p1:                                          # differences, never |a|^2 + |b|^2 - 2ab
+        diff = p2 - row
+        total += float(np.sqrt(np.einsum("ij,ij->i", diff, diff)).sum())
+    return center, std1, std2, total / (len(p1) * len(p2))
+
+
+def compute_distance_metrics(points1, points2) -> tuple[float, float, float, float] | None:
+    """``(center_distance, std1, std2, mean_cross_distance)`` of two point clouds ``[N1, D]`` / ``[N2, D]``, or ``None``
+    when one is empty.  Device tensors go through ``ops.latent_group_stats`` (one segment); anything else is computed
+    in fp64 numpy."""
+    if len(points1) == 0 or len(points2) == 0:
+        return None
+    if _is_device_tensor(points1) and _is_device_tensor(points2):
+        from .. import ops
+        seg1 = torch.tensor([0, points1.shape[0]], dtype=torch.int32, device=points1.device)
+        seg2 = torch.tensor([0, points2.shape[0]], dtype=torch.int32, device=points1.device)
+        row = ops.latent_group_stats(points1, seg1, points2, seg2)[0].cpu().tolist()
+        return row[0], row[1], row[2], row[3]
+    if isinstance(points1, torch.Tensor):
+        points1 = points1.detach().cpu().numpy()
+    if isinstance(points2, torch.Tensor):
+        points2 = points2.detach().cpu().numpy()
+    return _host_metrics(np.array(points1), np.array(points2))
+
+
+def segmented_distance_metrics_host(points1, seg1, points2, seg2) -> np.ndarray:
+    """fp64 numpy statement of ``ops.latent_group_stats``: ``[patients, 4]``, NaN rows for patients without rows on one side."""
+    points1, points2 = np.asarray(points1), np.asarray(points2)
+    out = np.full((len(seg1) - 1, 4), np.nan)
+    for e in range(len(seg1) - 1):
+        a, b = points1[seg1[e]:seg1[e + 1]], points2[seg2[e]:seg2[e + 1]]
+        if len(a) and len(b):
+            out[e] = _host_metrics(a, b)
+    return out
+
+
+def group_rows_by_patient(ids1: list[str], ids2: list[str]) -> tuple[list[str], list[int], list[int], list[int], list[int]]:
+    """-> (sorted patients of either group, row order 1, offsets 1, row order 2, offsets 2): ``order`` lists each group's
+    row indices patient by patient (original order inside a patient), ``offsets[p] .. offsets[p + 1]`` are patient p's."""
+    patients = sorted(set(ids1) | set(ids2))
+    slot = {p: i for i, p in enumerate(patients)}
+
+    def one(ids):
+        rows: list[list[int]] = [[] for _ in patients]
+        for i, p in enumerate(ids):
+            rows[slot[p]].append(i)
+        order = [i for r in rows for i in r]
+        offsets = [0]
+        for r in rows:
+            offsets.append(offsets[-1] + len(r))
+        return order, offsets
+
+    order1, off1 = one(ids1)
+    order2, off2 = one(ids2)
+    return patients, order1, off1, order2, off2
+
+
+def write_group_statistics(patients, counts1, counts2, metrics_lat, metrics_proj, name1: str, name2: str, output_dir) -> None:
+    """``distance_metrics.txt`` and ``exams_sorted_by_distance.txt`` in the reference's text format.  ``metrics_*``:
+    ``[patients, 4]``; a patient without rows in one group is left out."""
+    output_dir = Path(output_dir)
+    ranked = []
+    with open(output_dir / "distance_metrics.txt", "w") as f:
+        f.write("Distance Metrics per Exam (Latent Space and Projection)\n")
+        f.write("=" * 60 + "\n\n")
+        for p, exam in enumerate(patients):
+            if counts1[p] == 0 or counts2[p] == 0:
+                continue
+            lat, proj = [float(v) for v in metrics_lat[p]], [float(v) for v in metrics_proj[p]]
+            f.write(f"{exam}\n")
+            f.write(f"  - n_{name1}: {counts1[p]}, n_{name2}: {counts2[p]}\n")
+            for tag, m, end in (("Latent", lat, "\n"), ("Projection", proj, "\n\n")):
+                f.write(f"  - [{tag}] center_dist: {m[0]:.3f}, std_{name1}: {m[1]:.3f}, std_{name2}: {m[2]:.3f}, "
+                        f"mean_cross_dist: {m[3]:.3f}{end}")
+            ranked.append((exam, lat[0]))
+    ranked.sort(key=lambda item: item[1])
+    with open(output_dir / "exams_sorted_by_distance.txt", "w") as f:
+        f.write("Exams sorted by latent space center distance\n")
+        f.write("=" * 60 + "\n\n")
+        for exam, dist in ranked:
+            f.write(f"{exam}: {dist:.3f}\n")
+
+
+class LatentSpaceAnalyzer:
+    """Encode images to latents, reduce them (PCA, then optionally t-SNE / UMAP) and compare two groups per patient.
+
+    ``vae_model``: a model with ``encode_deterministic``; ``device``: the HIP device; ``transform``: what turns paths
+    into network inputs -- either an object with ``loader(paths, batch_size)`` that yields device batches
+    ``[b, C, H, W]`` (``analyze_static.TiffPreprocess``), or a callable ``path -> [C, H, W]`` tensor as in the reference."""
+
+    def __init__(self, vae_model: torch.nn.Module, device: torch.device, transform) -> None:
+        self.vae = vae_model
+        self.device = device
+        self.transform = transform
+        self.vae.eval()
+
+    # ---- encoding ----
+    def _batches(self, image_paths: list[str], batch_size: int):
+        if hasattr(self.transform, "loader"):
+            yield from self.transform.loader(image_paths, batch_size)
+            return
+        for i in range(0, len(image_paths), batch_size):
+            yield torch.stack([torch.as_tensor(self.transform(p)) for p in image_paths[i:i + batch_size]]).to(self.device)
+
+    def encode_images(self, image_paths: list[str], max_images: int | None = None, batch_size: int = 8,
+                      show_progress: bool = True, return_device: bool = False):
+        """-> (latents ``[N, D]``, patient ids).  Deterministic (``z_mu``) and bit-exactly independent of the batch size.
+        Every batch's ``z_mu`` is written, flattened in (C, H, W) order, into one preallocated device matrix; the host
+        gets it in ONE copy at the end -- or not at all with ``return_device=True``, which returns the device matrix."""
+        if len(image_paths) == 0:
+            raise ValueError("image_paths cannot be empty")
+        if max_images is not None:
+            image_paths = image_paths[:max_images]
+        batches = self._batches(list(image_paths), batch_size)
+        if show_progress:
+            try:
+                from tqdm import tqdm
+                batches = tqdm(batches, total=-(-len(image_paths) // batch_size), desc="Encoding images", unit="batch")
+            except ImportError:
+                pass
+        matrix, row = None, 0
+        with torch.no_grad():
+            for batch in batches:
+                z = self.vae.encode_deterministic(batch.to(self.device)).flatten(start_dim=1)
+                if matrix is None:
+                    matrix = torch.empty(len(image_paths), z.shape[1], dtype=torch.float32, device=z.device)
+                matrix[row:row + z.shape[0]].copy_(z)
+                row += z.shape[0]
+        if row != len(image_paths):
+            raise RuntimeError(f"encoded {row} of {len(image_paths)} images")
+        ids = [extract_patient_id_from_filename(os.path.basename(p)) for p in image_paths]
+        return (matrix if return_device else matrix.cpu().numpy()), ids
+
+    # ---- dimensionality reduction ----
+    def _to_device_matrix(self, x) -> torch.Tensor:
+        if isinstance(x, torch.Tensor):
+            return x.to(self.device, torch.float32)
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
+
+    def reduce_dimensionality_pca(self, latent_vectors, n_components: int = 50) -> tuple[np.ndarray, np.ndarray]:
+        """-> (projections ``[N, n_components]`` fp64, explained-variance ratios).  The column mean and the centred Gram
+        matrix ``G = Xc Xc^T`` are computed on the device; ``G = U diag(lambda) U^T`` in fp64 on the host, and the
+        projections are ``U sqrt(lambda)`` -- what ``PCA(svd_solver="full").fit_transform`` returns.  Signs: the entry of
+        largest magnitude of each column of U is positive (sklearn's ``svd_flip``, u-based)."""
+        from .. import ops
+        if latent_vectors.ndim != 2:
+            raise ValueError(f"Expected 2D array, got {latent_vectors.ndim}D array")
+        n, d = latent_vectors.shape
+        if not 1 <= n_components <= min(n, d):
+            raise ValueError(f"n_components={n_components} must be between 1 and min(n_samples, n_features)={min(n, d)}")
+        x = self._to_device_matrix(latent_vectors)
+        gram = ops.latent_pairwise(x, mode="dot", center=x.mean(dim=0)).cpu().double().numpy()
+        lam, u = np.linalg.eigh(gram)
+        lam, u = np.clip(lam[::-1], 0.0, None), u[:, ::-1]
+        total = float(np.trace(gram))
+        lam, u = lam[:n_components], u[:, :n_components].copy()
+        top = np.argmax(np.abs(u), axis=0)
+        signs = np.sign(u[top, np.arange(n_components)])
+        signs[signs == 0] = 1.0
+        return u * signs * np.sqrt(lam), (lam / total if total > 0 else np.zeros_like(lam))
+
+    @staticmethod
+    def _check_reduction_input(latent_vectors, pca_components: int) -> int:
+        if latent_vectors.ndim != 2:
+            raise ValueError(f"Expected 2D array, got {latent_vectors.ndim}D array")
+        n_samples = len(latent_vectors)
+        if n_samples < pca_components:
+            raise ValueError(f"Need at least {pca_components} samples for PCA with {pca_components} components, "
+                             f"got {n_samples} samples. Reduce pca_components or provide more samples.")
+        return n_samples
+
+    def reduce_dimensionality_umap(self, latent_vectors, n_components: int = 2, n_neighbors: int = 40, min_dist: float = 0.5,
+                                   random_state: int = 42, pca_components: int = 50) -> tuple[np.ndarray, object]:
+        """PCA, then UMAP on the host -> (reduced ``[N, n_components]``, the fitted UMAP model)."""
+        n_samples = self._check_reduction_input(latent_vectors, pca_components)
+        if n_neighbors >= n_samples:
+            raise ValueError(f"n_neighbors ({n_neighbors}) must be < n_samples ({n_samples}). "
+                             f"Reduce n_neighbors or provide more samples.")
+        try:
+            import umap
+        except ImportError as e:
+            raise ImportError("Please install umap-learn: pip install umap-learn") from e
+        vectors_pca, _ = self.reduce_dimensionality_pca(latent_vectors, pca_components)
+        model = umap.UMAP(n_components=n_components, random_state=random_state, n_neighbors=n_neighbors, min_dist=min_dist)
+        return model.fit_transform(vectors_pca), model
+
+    def reduce_dimensionality_tsne(self, latent_vectors, n_components: int = 2, perplexity: int = 30, random_state: int = 42,
+                                   pca_components: int = 50) -> np.ndarray:
+        """PCA, then t-SNE on the host -> reduced ``[N, n_components]``."""
+        n_samples = self._check_reduction_input(latent_vectors, pca_components)
+        if perplexity >= n_samples:
+            raise ValueError(f"perplexity ({perplexity}) must be < n_samples ({n_samples}). "
+                             f"Reduce perplexity or provide more samples.")
+        if perplexity < 5:
+            print(f"Warning: perplexity={perplexity} is very low. Consider using 5-50 for better results.")
+        try:
+            from sklearn.manifold import TSNE
+        except ImportError as e:
+            raise ImportError("Please install scikit-learn: pip install scikit-learn") from e
+        vectors_pca, _ = self.reduce_dimensionality_pca(latent_vectors, pca_components)
+        return TSNE(n_components=n_components, perplexity=perplexity, init="pca", random_state=random_state).fit_transform(vectors_pca)
+
+    # ---- colours ----
+    def create_patient_colormap(self, patient_ids: list[str]) -> tuple[dict[str, int], dict[str, str]]:
+        """-> (patient -> index in sorted order, patient -> hex colour, cycling through ``PATIENT_PALETTE``)."""
+        patients = sorted(set(patient_ids))
+        return ({p: i for i, p in enumerate(patients)},
+                {p: PATIENT_PALETTE[i % len(PATIENT_PALETTE)] for i, p in enumerate(patients)})
+
+    def save_color_legend(self, exam_to_id: dict[str, int], exam_to_color: dict[str, str], output_path: Path) -> None:
+        with open(output_path, "w") as f:
+            f.write("Color Legend for Exams\n")
+            f.write("=" * 60 + "\n\n")
+            for exam in sorted(exam_to_id, key=exam_to_id.get):
+                f.write(f"{exam_to_id[exam]}: {exam} — {exam_to_color[exam]}\n")
+
+    # ---- statistics ----
+    def _segmented_metrics(self, points1, seg1, points2, seg2) -> np.ndarray:
+        """``[patients, 4]`` from one ``ops.latent_group_stats`` call; the rows are already grouped by patient."""
+        from .. import ops
+        s1 = torch.tensor(seg1, dtype=torch.int32, device=self.device)
+        s2 = torch.tensor(seg2, dtype=torch.int32, device=self.device)
+        return ops.latent_group_stats(self._to_device_matrix(points1), s1, self._to_device_matrix(points2), s2).cpu().double().numpy()
+
+    @staticmethod
+    def _take_rows(points, order):
+        if isinstance(points, torch.Tensor):
+            return points.index_select(0, torch.tensor(order, dtype=torch.int64, device=points.device))
+        return np.asarray(points)[np.asarray(order, dtype=np.int64)]
+
+    def compute_group_statistics(self, projections: list, latent_vectors_list: list, output_dir: Path) -> None:
+        """``projections`` / ``latent_vectors_list``: two ``(vectors, ids, name)`` tuples each (numpy arrays or device
+        tensors).  Rows are grouped by patient id, patients sorted; one device call gives the four metrics of every
+        patient in latent space, a second one in the projection; writes ``distance_metrics.txt`` and
+        ``exams_sorted_by_distance.txt``.  Anything but two groups: nothing is written, as in the reference."""
+        if len(projections) != 2 or len(latent_vectors_list) != 2:
+            return
+        (proj1, ids1, name1), (proj2, ids2, name2) = projections
+        lat1, lat2 = latent_vectors_list[0][0], latent_vectors_list[1][0]
+        patients, order1, seg1, order2, seg2 = group_rows_by_patient(list(ids1), list(ids2))
+        counts1 = [seg1[p + 1] - seg1[p] for p in range(len(patients))]
+        counts2 = [seg2[p + 1] - seg2[p] for p in range(len(patients))]
+        if not order1 or not order2:
+            nan = np.full((len(patients), 4), np.nan)
+            write_group_statistics(patients, counts1, counts2, nan, nan, name1, name2, output_dir)
+            return
+        metrics_lat = self._segmented_metrics(self._take_rows(lat1, order1), seg1, self._take_rows(lat2, order2), seg2)
+        metrics_proj = self._segmented_metrics(self._take_rows(proj1, order1), seg1, self._take_rows(proj2, order2), seg2)
+        write_group_statistics(patients, counts1, counts2, metrics_lat, metrics_proj, name1, name2, output_dir)

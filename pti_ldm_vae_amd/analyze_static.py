@@ -1,0 +1,199 @@
+#!/usr/bin/env python3
+"""Static latent-space analysis of a trained VAE -- the counterpart of the reference's ``vae_scripts/analyze_static.py``.
+
+    python -m pti_ldm_vae_amd.analyze_static --vae-weights W.pth --config-file CFG.json --folder-edente DIR [--folder-dente DIR]
+
+Same options and defaults, plus ``--method pca`` (the projection is the first two principal components; also the
+fallback, with a warning, when umap-learn / scikit-learn is not installed), ``--cache-dir`` and ``--batch-size``.
+Outputs in ``--output-dir``: ``<method>_projection.png`` (matplotlib; ``.html`` through plotly when that fails),
+``color_legend.txt`` with ``--color-by-patient``, and with two groups ``distance_metrics.txt``,
+``exams_sorted_by_distance.txt`` and ``latents.npz`` (latents, ids, paths and projection of each group).
+
+Images are encoded deterministically in batches on the HIP engine; each image's latent is cached on disk in the
+reference's layout (``analysis.LatentCache``), so a second run on the same folders encodes nothing."""
+from __future__ import annotations
+
+import argparse
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from .analysis import LatentCache, LatentSpaceAnalyzer, load_image_paths
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    parser = argparse.ArgumentParser(description="Static Latent Space Analysis (UMAP, t-SNE or PCA; MI355X, HIP engine)")
+    parser.add_argument("--vae-weights", type=str, required=True, help="Path to VAE weights file")
+    parser.add_argument("--config-file", type=str, required=True, help="Path to model config file")
+    parser.add_argument("--folder-edente", type=str, required=True, help="Path to edentulous image group folder")
+    parser.add_argument("--folder-dente", type=str, default=None, help="Path to dentulous image group folder (optional)")
+    parser.add_argument("--output-dir", type=str, default="projections", help="Output directory for projections")
+    parser.add_argument("--max-images", type=int, default=1000, help="Maximum number of images per group")
+    parser.add_argument("--patch-size", type=int, nargs=2, default=[256, 256], help="Image patch size (H W)")
+    parser.add_argument("--color-by-patient", action="store_true", help="Color points by patient ID instead of group")
+    parser.add_argument("--method", type=str, choices=["umap", "tsne", "pca"], default="umap",
+                        help="Dimensionality reduction method (default: umap)")
+    parser.add_argument("--n-neighbors", type=int, default=40, help="UMAP n_neighbors parameter")
+    parser.add_argument("--min-dist", type=float, default=0.5, help="UMAP min_dist parameter")
+    parser.add_argument("--perplexity", type=int, default=30, help="t-SNE perplexity parameter")
+    parser.add_argument("--seed", type=int, default=42, help="Random seed for reproducibility")
+    parser.add_argument("--subtitle", type=str, default=None, help="Optional subtitle for the plot")
+    parser.add_argument("--dpi", type=int, default=300, help="DPI for output PNG (default: 300)")
+    parser.add_argument("--cache-dir", type=str, default="cache/latents", help="Root of the per-image latent cache")
+    parser.add_argument("--batch-size", type=int, default=8, help="Images per encoder call (default: 8)")
+    return parser.parse_args(argv)
+
+
+class TiffPreprocess:
+    """The training pipeline's preprocessing (TIFF decode, area resize, masked z-score) for lists of paths:
+    ``loader(paths, batch_size)`` yields device batches ``[b, 1, H, W]``; called with one path it returns ``[1, H, W]``."""
+
+    def __init__(self, patch_size: tuple[int, int], device, num_workers: int = 4) -> None:
+        self.patch_size, self.device, self.num_workers = tuple(patch_size), device, num_workers
+
+    def loader(self, paths: list[str], batch_size: int):
+        from .data import DeviceImageLoader
+        return DeviceImageLoader(paths, batch_size, self.patch_size, self.device, shuffle=False, num_workers=self.num_workers)
+
+    def __call__(self, path: str) -> torch.Tensor:
+        return next(iter(self.loader([path], 1)))[0].clone()
+
+
+def load_and_encode_group_with_cache(analyzer: LatentSpaceAnalyzer, folder_path: str, vae_weights: str, max_images: int,
+                                     patch_size: tuple[int, int], group_name: str, cache_dir=Path("cache/latents"),
+                                     batch_size: int = 8) -> tuple[np.ndarray, list[str], list[str]]:
+    """-> (latents, patient ids, paths) of the folder's images; only images missing from the cache are encoded, all of
+    them in batches of ``batch_size``."""
+    paths = load_image_paths(folder_path, max_images)
+    if not paths:
+        raise FileNotFoundError(f"No .tif/.tiff images found in {folder_path}")
+
+    def encode_many(miss_paths):
+        return analyzer.encode_images(miss_paths, batch_size=batch_size, show_progress=False)
+
+    def encode_one(path):
+        latents, ids = encode_many([path])
+        return latents[0], ids[0]
+
+    return LatentCache(cache_root=Path(cache_dir)).get_or_encode_batch(paths, encode_one, vae_weights, tuple(patch_size),
+                                                                       group_name, encode_many=encode_many)
+
+
+def project(analyzer: LatentSpaceAnalyzer, latents: np.ndarray, args: argparse.Namespace) -> tuple[np.ndarray, str]:
+    """-> (2-D projection of all rows, the method that produced it).  A missing host library falls back to PCA."""
+    n = len(latents)
+    if args.method != "pca":
+        try:
+            if args.method == "umap":
+                return analyzer.reduce_dimensionality_umap(latents, n_neighbors=args.n_neighbors, min_dist=args.min_dist,
+                                                           random_state=args.seed, pca_components=min(n, 50))[0], "umap"
+            print("(This may take a few minutes...)")
+            return analyzer.reduce_dimensionality_tsne(latents, perplexity=args.perplexity, random_state=args.seed,
+                                                       pca_components=min(n, 50)), "tsne"
+        except ImportError as e:
+            print(f"[WARN] --method {args.method} is not available ({e}); falling back to --method pca")
+    if n < 2:
+        raise SystemExit("analyze_static: a PCA projection needs at least two images")
+    proj, ratio = analyzer.reduce_dimensionality_pca(latents, 2)
+    print(f"PCA explained variance ratio: {ratio[0]:.4f}, {ratio[1]:.4f}")
+    return proj, "pca"
+
+
+def save_projection_plot(groups: list, output_path: Path, title: str, subtitle: str | None, dpi: int,
+                         patient_to_color: dict | None) -> Path:
+    """``groups``: ``(points [n, 2], ids, name)``; edente = open circles, dente = filled.  -> the file written: the PNG
+    through matplotlib, or an HTML file through plotly when matplotlib cannot be used."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+        fig, ax = plt.subplots(figsize=(8, 7))
+        for k, (pts, ids, name) in enumerate(groups):
+            filled = "dente" in name.lower() and "edente" not in name.lower()
+            colors = [patient_to_color[i] for i in ids] if patient_to_color else ("#1f77b4" if k == 0 else "#ff7f0e")
+            ax.scatter(pts[:, 0], pts[:, 1], s=36, alpha=0.7, linewidths=1.0, label=name, edgecolors=colors,
+                       facecolors=colors if filled else "none")
+        ax.set_xlabel("Dimension 1")
+        ax.set_ylabel("Dimension 2")
+        ax.set_title(title if not subtitle else f"{title}\n{subtitle}")
+        ax.grid(True, color="lightgray")
+        fig.savefig(output_path, dpi=dpi)
+        plt.close(fig)
+        return output_path
+    except Exception as e:
+        try:
+            import plotly.graph_objects as go
+        except ImportError:
+            raise e
+        fig = go.Figure()
+        for k, (pts, ids, name) in enumerate(groups):
+            filled = "dente" in name.lower() and "edente" not in name.lower()
+            colors = [patient_to_color[i] for i in ids] if patient_to_color else ("#1f77b4" if k == 0 else "#ff7f0e")
+            fig.add_trace(go.Scatter(x=pts[:, 0], y=pts[:, 1], mode="markers", name=name, text=list(ids),
+                                     marker={"color": colors, "symbol": "circle" if filled else "circle-open", "size": 10}))
+        fig.update_layout(title=title if not subtitle else f"{title}<br><sub>{subtitle}</sub>", xaxis_title="Dimension 1",
+                          yaxis_title="Dimension 2", template="plotly_white")
+        html_path = output_path.with_suffix(".html")
+        fig.write_html(str(html_path))
+        print(f"⚠️  Could not export PNG ({e}). Saved HTML instead: {html_path}")
+        return html_path
+
+
+def main(argv=None) -> None:
+    from . import _lib
+    from .utils.cli_common import init_device_and_seed, load_config_and_model
+    _lib.refuse_wrong_result_env("analyze_static.py")
+    args = parse_args(argv)
+    device = init_device_and_seed(args.seed)
+    np.random.seed(args.seed)
+    output_dir = Path(args.output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+    print("=" * 60)
+    print(f"Static Latent Space Analysis - {args.method.upper()}")
+    print("=" * 60)
+    _, vae = load_config_and_model(args.config_file, args.vae_weights, device)
+    print(f"Loaded VAE from {args.vae_weights}")
+    patch = (int(args.patch_size[0]), int(args.patch_size[1]))
+    analyzer = LatentSpaceAnalyzer(vae, device, TiffPreprocess(patch, device))
+
+    groups = []                                             # (latents, ids, paths, name)
+    for folder, name in ((args.folder_edente, "edente"), (args.folder_dente, "dente")):
+        if folder:
+            latents, ids, paths = load_and_encode_group_with_cache(analyzer, folder, args.vae_weights, args.max_images, patch,
+                                                                   name, cache_dir=args.cache_dir, batch_size=args.batch_size)
+            groups.append((latents, ids, paths, name))
+
+    print(f"Computing {args.method.upper()} projection...")
+    combined = np.concatenate([g[0] for g in groups]) if len(groups) > 1 else groups[0][0]
+    projection, method = project(analyzer, combined, args)
+    split = len(groups[0][0])
+    projected = [projection[:split]] + ([projection[split:]] if len(groups) > 1 else [])
+
+    title = {"umap": "UMAP", "tsne": "t-SNE", "pca": "PCA"}[method]
+    if len(groups) > 1:
+        title = f"{title} (● dente, ○ edente)"
+    patient_to_color = None
+    if args.color_by_patient:
+        patient_to_id, patient_to_color = analyzer.create_patient_colormap([i for g in groups for i in g[1]])
+        analyzer.save_color_legend(patient_to_id, patient_to_color, output_dir / "color_legend.txt")
+        print(f"✅ Color legend saved: {output_dir / 'color_legend.txt'}")
+    written = save_projection_plot([(p, g[1], g[3]) for p, g in zip(projected, groups)], output_dir / f"{method}_projection.png",
+                                   title, args.subtitle, args.dpi, patient_to_color)
+    print(f"✅ Visualization saved: {written}")
+
+    if len(groups) > 1:
+        analyzer.compute_group_statistics([(p, g[1], g[3]) for p, g in zip(projected, groups)],
+                                          [(g[0], g[1], g[3]) for g in groups], output_dir)
+        arrays = {}
+        for p, (latents, ids, paths, name) in zip(projected, groups):
+            arrays.update({f"latents_{name}": latents, f"ids_{name}": np.array(ids), f"paths_{name}": np.array(paths),
+                           f"projection_{name}": p})
+        np.savez(output_dir / "latents.npz", **arrays)
+        print(f"✅ Statistics saved to {output_dir}/distance_metrics.txt")
+        print(f"✅ Sorted exams saved to {output_dir}/exams_sorted_by_distance.txt")
+    print("✅ Analysis complete!")
+
+
+if __name__ == "__main__":
+    main()

@@ -811,6 +811,114 @@ def image_metrics(pred, target, *, clamp=None, data_range=1.0, k1=0.01, k2=0.03,
     return out
 
 
+# ---- latent-space analysis (csrc/latent_stats.hip; include/pti_vae.h "latent-space analysis") -------------------------
+_latent_ws = {}
+
+
+def _rows(t, name):
+    """-> ``t`` as an fp32 device matrix whose rows are dense (column stride 1, row stride >= columns); a view that
+    already is one (a row-strided slice included) is passed through without a copy."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
+    if not t.is_floating_point():
+        raise TypeError(f"{name}: expected a floating-point matrix, got {t.dtype}")
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name}: expected a non-empty [n, d] matrix, got {tuple(t.shape)}")
+    if t.dtype != F32:
+        t = t.to(F32)
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t
+
+
+def _latent_out(out, shape, like, name):
+    if out is None:
+        return torch.empty(shape, dtype=F32, device=like.device)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda:
+        raise ValueError(f"{name}: out must be a CUDA(HIP) tensor")
+    if out.dtype != F32:
+        raise TypeError(f"{name}: out must be fp32, got {out.dtype}")
+    if tuple(out.shape) != tuple(shape) or out.device != like.device or out.stride(1) != 1 or out.stride(0) < shape[1]:
+        raise ValueError(f"{name}: out must be {list(shape)} on {like.device} with dense rows")
+    return out
+
+
+def _latent_workspace(kind, shape, floats, device, stream):
+    key = (kind, device.index, stream) + tuple(shape)
+    ws = _latent_ws.get(key)
+    if ws is None:
+        ws = _latent_ws[key] = torch.empty(floats, dtype=F32, device=device)
+    return ws
+
+
+def latent_pairwise(a, b=None, *, mode="dist", center=None, out=None):
+    """``out[i, j]`` = Euclidean distance (``mode="dist"``) or dot product (``mode="dot"``) of row ``i`` of ``a`` [n1, d]
+    and row ``j`` of ``b`` [n2, d] (``b=None``: ``a`` against itself) -> fp32 ``[n1, n2]`` device tensor
+    (``pti_latent_pairwise``).  ``center`` [d] is subtracted from both as they are loaded: ``mode="dot"`` with the column
+    mean is the centred Gram matrix.  Distances are accumulated as sum (a - b)^2 in fp32 in a fixed order: bitwise
+    reproducible, and an entry depends on its two rows only.  Row-strided views and an ``out`` view with a row stride
+    are used in place.  Runs on the current stream, no host sync; the scratch buffer is cached per (stream, shape)."""
+    if mode not in ("dist", "dot"):
+        raise ValueError(f"latent_pairwise: mode must be 'dist' or 'dot', got {mode!r}")
+    a = _rows(a, "latent_pairwise: a")
+    b = a if b is None else _rows(b, "latent_pairwise: b")
+    if b.shape[1] != a.shape[1] or b.device != a.device:
+        raise ValueError(f"latent_pairwise: a {tuple(a.shape)} and b {tuple(b.shape)} must share columns and device")
+    n1, d = a.shape
+    n2 = b.shape[0]
+    if center is not None:
+        if not isinstance(center, torch.Tensor) or not center.is_cuda:
+            raise ValueError("latent_pairwise: center must be a CUDA(HIP) tensor")
+        if not center.is_floating_point():
+            raise TypeError("latent_pairwise: center must be floating-point")
+        if center.numel() != d or center.device != a.device:
+            raise ValueError(f"latent_pairwise: center must hold {d} values on {a.device}")
+        center = center.reshape(-1).to(F32).contiguous()
+    floats = L.lib().pti_latent_pairwise_ws_floats(n1, n2, d)
+    if floats <= 0:
+        raise ValueError(f"latent_pairwise: unsupported shape a {tuple(a.shape)} b {tuple(b.shape)}")
+    out = _latent_out(out, (n1, n2), a, "latent_pairwise")
+    stream = _stream()
+    ws = _latent_workspace("pair", (n1, n2, d), floats, a.device, stream)
+    L.check(L.lib().pti_latent_pairwise(_ptr(a), a.stride(0), n1, _ptr(b), b.stride(0), n2, d, _ptr(center),
+                                        int(mode == "dot"), _ptr(out), out.stride(0), _ptr(ws), stream), "pti_latent_pairwise")
+    return out
+
+
+def latent_group_stats(a, seg_a, b, seg_b, *, out=None):
+    """Per-patient distance statistics of two groups of rows (``pti_latent_group_stats``) -> fp32 ``[patients, 4]``:
+    (centre distance, mean population std of the ``a`` rows, the same for ``b``, mean cross distance), the reference's
+    ``compute_distance_metrics`` for every patient at once.  ``a`` [n1, d] / ``b`` [n2, d] hold each patient's rows
+    consecutively; ``seg_a`` / ``seg_b`` are int32 device vectors of ``patients + 1`` ascending row offsets.  A patient
+    without rows on one side gets a NaN row.  Runs on the current stream, no host sync."""
+    a = _rows(a, "latent_group_stats: a")
+    b = _rows(b, "latent_group_stats: b")
+    if b.shape[1] != a.shape[1] or b.device != a.device:
+        raise ValueError(f"latent_group_stats: a {tuple(a.shape)} and b {tuple(b.shape)} must share columns and device")
+    for name, seg in (("seg_a", seg_a), ("seg_b", seg_b)):
+        if not isinstance(seg, torch.Tensor) or not seg.is_cuda or seg.device != a.device:
+            raise ValueError(f"latent_group_stats: {name} must be a CUDA(HIP) tensor on {a.device}")
+        if seg.dtype != torch.int32:
+            raise TypeError(f"latent_group_stats: {name} must be int32, got {seg.dtype}")
+        if seg.dim() != 1 or seg.numel() < 2 or not seg.is_contiguous():
+            raise ValueError(f"latent_group_stats: {name} must be a contiguous vector of patients + 1 offsets")
+    if seg_a.numel() != seg_b.numel():
+        raise ValueError("latent_group_stats: seg_a and seg_b must describe the same patients")
+    e = seg_a.numel() - 1
+    (n1, d), n2 = a.shape, b.shape[0]
+    floats = L.lib().pti_latent_group_stats_ws_floats(n1, n2, e, d)
+    if floats <= 0:
+        raise ValueError(f"latent_group_stats: unsupported shape a {tuple(a.shape)} b {tuple(b.shape)} patients {e}")
+    out = _latent_out(out, (e, 4), a, "latent_group_stats")
+    if out.stride(0) != 4:
+        raise ValueError("latent_group_stats: out must be contiguous")
+    stream = _stream()
+    ws = _latent_workspace("group", (n1, n2, e, d), floats, a.device, stream)
+    L.check(L.lib().pti_latent_group_stats(_ptr(a), a.stride(0), n1, _ptr(seg_a), _ptr(b), b.stride(0), n2, _ptr(seg_b), e, d,
+                                           _ptr(out), _ptr(ws), stream), "pti_latent_group_stats")
+    return out
+
+
 # ---- PatchDiscriminator passes (csrc/discriminator.hip; include/pti_vae.h "PatchDiscriminator") -----------------------
 def pd_out_hw(h, w, stride):
     return (h + 2 - 4) // stride + 1, (w + 2 - 4) // stride + 1
