@@ -17,6 +17,7 @@ from __future__ import annotations
 import contextlib
 import gc
 import os
+import warnings
 
 import torch
 
@@ -54,6 +55,29 @@ def gc_off_for_capture():
     finally:
         if enabled:
             gc.enable()
+
+
+def capture_or_eager(what, *bodies):
+    """The whole "capture a HIP graph, fall back to eager launches" recipe.  Captures each of ``bodies`` into a
+    ``torch.cuda.CUDAGraph`` of its own and returns (graphs, results); a body is called with the results of the bodies
+    before it.  Graphs after the first share the first one's memory pool (tensors cross from one to the next: the
+    data-parallel step's two halves), and all of them are captured under ONE ``gc_off_for_capture()``.  A capture that
+    fails must not take the run down: on any exception this warns (naming ``what``), synchronises and returns None, and
+    the caller clears its own flag and runs eagerly from there on."""
+    graphs, results = [], []
+    try:
+        with gc_off_for_capture():
+            for body in bodies:
+                g = torch.cuda.CUDAGraph()
+                # (thread_local: loader threads may issue copies meanwhile)
+                with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None, capture_error_mode="thread_local"):
+                    results.append(body(*results))
+                graphs.append(g)
+    except Exception as ex:
+        warnings.warn(f"HIP-graph capture of {what} failed ({ex!r}); continuing with eager launches")
+        torch.cuda.synchronize()
+        return None
+    return graphs, results
 
 
 # =================================================================================================
@@ -96,12 +120,6 @@ class _MfmaConv:
             return g[o:o + 3 * n], g[ob:ob + 3 * nb]
         return self.net.grad_view(self.wname).view(-1), self.net.grad_view(self.bname)
 
-    def repack(self):
-        w = self._w()
-        self.wp = ops.pack_conv_weight(w, self.ksize, self.mode, out=self.wp, f16=self.f16)
-        dmode = PTI_CONV_ZINS if self.mode == PTI_CONV_S2PAD else PTI_CONV_S1
-        self.wpt = ops.pack_conv_weight(w, self.ksize, dmode, flip=True, out=self.wpt)
-
     # y = conv(prologue(x)) + b [+ residual]; optional fused stats of y
     def fwd(self, x, *, pro=PTI_PRO_NONE, norm=None, residual=None, want_stats=False, eng=None, act_out=None,
             out_dtype=None):
@@ -133,13 +151,14 @@ class _MfmaConv:
     def dgrad_gn(self, dy, x, norm, *, silu, dres, eng):
         """Data gradient through  conv(act(GN(x)))  down to dx: the conv^T launch also does the GroupNorm
         backward reduction (fused epilogue), pti_gn_bwd_apply finishes.  Stride-1 convs only."""
-        n, ho, wo, _ = dy.shape
-        dyt = _empty((n, ho, wo, self.cin), dy)
-        sums = eng.zeros(n * self.cin * 2)
-        ops.conv_mfma_gnbwd(dy, self.wpt, x.t, x.stats, norm.weight.data, norm.bias.data, dyt, sums, cout=self.cin,
-                            ksize=self.ksize, mode=PTI_CONV_S1, groups=eng.G, eps=eng.eps, silu=silu)
+        g, sums = self.dgrad_gn_raw(dy, x, norm, silu=silu, eng=eng)
+        return self._gn_apply(g, sums, x, norm, dres, eng)
+
+    def _gn_apply(self, g, sums, x, norm, dres, eng):
+        """Second half of ``dgrad_gn``: pti_gn_bwd_apply turns (g, finalized sums) into dx [+ dres] and the affine
+        gradients of ``norm``."""
         dx = _empty(x.t.shape, x.t)
-        ops.gn_bwd_apply(x.t, dyt, dx, x.stats, norm.weight.data, norm.bias.data, sums,
+        ops.gn_bwd_apply(x.t, g, dx, x.stats, norm.weight.data, norm.bias.data, sums,
                          norm.net.grad_view(norm.prefix + ".weight"), norm.net.grad_view(norm.prefix + ".bias"),
                          groups=eng.G, eps=eng.eps, dres=dres)
         return dx
@@ -167,11 +186,7 @@ class _MfmaConv:
                                   norm.weight.data, norm.bias.data, dyt, sums, cout=self.cin, groups=eng.G, eps=eng.eps,
                                   silu=silu, in_dgamma=norm_in.net.grad_view(norm_in.prefix + ".weight"),
                                   in_dbeta=norm_in.net.grad_view(norm_in.prefix + ".bias"))
-        dx = _empty(x.t.shape, x.t)
-        ops.gn_bwd_apply(x.t, dyt, dx, x.stats, norm.weight.data, norm.bias.data, sums,
-                         norm.net.grad_view(norm.prefix + ".weight"), norm.net.grad_view(norm.prefix + ".bias"),
-                         groups=eng.G, eps=eng.eps, dres=dres)
-        return dx, dxin
+        return self._gn_apply(dyt, sums, x, norm, dres, eng), dxin
 
     def wgrad(self, x, dy, *, pro=PTI_PRO_NONE, norm=None, eng=None):
         dw, db = self.grads()
@@ -181,20 +196,8 @@ class _MfmaConv:
         g, b = (norm.weight.data, norm.bias.data) if norm is not None else (None, None)
         kw = dict(ksize=self.ksize, mode=self.mode, prologue=pro, in_stats=x.stats if pro else None, gamma=g, beta=b,
                   groups=eng.G, eps=eng.eps, accumulate=True)
-        ws = eng.wgrad_stream
-        if ws is None:
-            ops.conv_wgrad_mfma(x.t, dy, dw, db, workspace=eng.workspace, **kw)
-            return
-        # weight gradients are off the data-gradient chain: they run on a side stream, behind an event that marks
-        # "x and dy exist", and are joined before their gradients are used (Engine.join_wgrad)
-        cur = torch.cuda.current_stream()
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        ws.wait_event(ev)
-        eng.record_side(x.t, dy, dw, db, *kw.values())
-        with torch.cuda.stream(ws):
-            ops.conv_wgrad_mfma(x.t, dy, dw, db, workspace=eng.workspace_side, **kw)
-        eng._wgrad_pending = True
+        with eng.side_stream(x.t, dy, dw, db, *kw.values()) as workspace:
+            ops.conv_wgrad_mfma(x.t, dy, dw, db, workspace=workspace, **kw)
 
 
 class _Norm:
@@ -241,37 +244,38 @@ class _ResBlock:
             save.append((x, h1, a1, a2))
         return out
 
+    @staticmethod
+    def _wgrad(conv, x, norm, a, dy, eng):
+        """Weight gradient of a ResBlock conv from its saved activated input ``a`` = SiLU(GN(x)) when the forward pass
+        kept one (``fwd``), else from ``x`` through the GroupNorm+SiLU prologue."""
+        if a is not None:
+            conv.wgrad(_Act(a), dy, eng=eng)
+        else:
+            conv.wgrad(x, dy, pro=PTI_PRO_GN_SILU, norm=norm, eng=eng)
+
+    def _shortcut_bwd(self, x, dout, eng):
+        """Backward of the shortcut: returns its gradient w.r.t. the block's input (the residual term of the block's
+        data gradient) and issues ``nin``'s weight gradient."""
+        if self.nin is None:
+            return dout
+        dres = self.nin.dgrad(dout)
+        self.nin.wgrad(x, dout, eng=eng)
+        return dres
+
     def bwd(self, dout, saved, eng):
         x, h1, a1, a2 = saved
-        if a2 is not None:
-            self.conv2.wgrad(_Act(a2), dout, eng=eng)
-        else:
-            self.conv2.wgrad(h1, dout, pro=PTI_PRO_GN_SILU, norm=self.norm2, eng=eng)
+        self._wgrad(self.conv2, h1, self.norm2, a2, dout, eng)
         if eng.gnbwd_chain and ops.gnbwd_chain_supported(self.conv1.cout, self.conv1.cin, 3, x.t.dtype, eng.G):
             # the GroupNorm backward between the two convs is applied inside conv1's data-gradient launch: no
             # pti_gn_bwd_apply for norm2 (its affine gradients ride the finalize launch of conv1's data gradient)
             g2, sums2 = self.conv2.dgrad_gn_raw(dout, h1, self.norm2, silu=True, eng=eng)
-            if self.nin is None:
-                dres = dout
-            else:
-                dres = self.nin.dgrad(dout)
-                self.nin.wgrad(x, dout, eng=eng)
+            dres = self._shortcut_bwd(x, dout, eng)
             dx, dh1 = self.conv1.dgrad_gn_chain(g2, h1, self.norm2, sums2, x, self.norm1, silu=True, dres=dres, eng=eng)
-            if a1 is not None:
-                self.conv1.wgrad(_Act(a1), dh1, eng=eng)
-            else:
-                self.conv1.wgrad(x, dh1, pro=PTI_PRO_GN_SILU, norm=self.norm1, eng=eng)
+            self._wgrad(self.conv1, x, self.norm1, a1, dh1, eng)
             return dx
         dh1 = self.conv2.dgrad_gn(dout, h1, self.norm2, silu=True, dres=None, eng=eng)
-        if a1 is not None:
-            self.conv1.wgrad(_Act(a1), dh1, eng=eng)
-        else:
-            self.conv1.wgrad(x, dh1, pro=PTI_PRO_GN_SILU, norm=self.norm1, eng=eng)
-        if self.nin is None:
-            dres = dout
-        else:
-            dres = self.nin.dgrad(dout)
-            self.nin.wgrad(x, dout, eng=eng)
+        self._wgrad(self.conv1, x, self.norm1, a1, dh1, eng)
+        dres = self._shortcut_bwd(x, dout, eng)
         return self.conv1.dgrad_gn(dh1, x, self.norm1, silu=True, dres=dres, eng=eng)
 
 
@@ -414,20 +418,6 @@ class _DirectConv:
         return out
 
 
-class _Plan:
-    """Shared forward/backward driver over a block list."""
-
-    def __init__(self, net, eng):
-        self.net, self.eng = net, eng
-        self.layers = []
-
-    def all_convs(self):
-        out = []
-        for l in self.layers:
-            out += l.convs
-        return out
-
-
 # =================================================================================================
 # engine
 # =================================================================================================
@@ -462,7 +452,7 @@ class Engine:
         self.wgrad_batch_max = max(1, min(ops.L.WGRAD_BATCH_MAX, int(os.environ.get("PTI_WGRAD_BATCH", "16"))))
         self.batch_wgrad = self.wgrad_batch_max > 1
         self._wgrad_jobs, self._ready_queue = [], []
-        # inference encodes replay a HIP graph per input shape (see _encode_graphed)
+        # inference encodes replay a HIP graph per input shape (see _forward_graphed)
         self.encode_graphs = os.environ.get("PTI_ENCODE_GRAPH", "1") == "1"
         self._enc_graphs, self._dec_graphs, self._enc_graph_version = {}, {}, None
         ops.L.lib()  # fail loudly now if the HIP extension is missing
@@ -630,19 +620,31 @@ class Engine:
             self._ready(l.prefix)
         return dout
 
-    def _wgrad_direct(self, wide, narrow, *args, **kw):
-        """ops.wgrad_direct on the weight-gradient side stream (same protocol as _MfmaConv.wgrad)."""
+    @contextlib.contextmanager
+    def side_stream(self, *operands):
+        """The one way work gets onto the weight-gradient side stream: ``with eng.side_stream(*operands) as workspace:``
+        runs its body there and yields the split-K workspace that belongs to that stream.  Weight gradients are off the
+        data-gradient chain: they run on the side stream behind an event that marks "everything the current stream has
+        issued so far" (so the operands exist), every temporary among ``operands`` -- ALL tensors the body reads or
+        writes -- is recorded on the side stream first (``record_side``), and the gradients are joined before they are
+        used (``join_wgrad``).  The stream is looked up per call (it can be switched off between steps); without one the
+        body runs on the current stream with the main workspace and nothing else happens."""
         ws = self.wgrad_stream
         if ws is None:
-            ops.wgrad_direct(wide, narrow, *args, **kw)
+            yield self.workspace
             return
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         ws.wait_event(ev)
-        self.record_side(wide, narrow, *args, *kw.values())
+        self.record_side(*operands)
         with torch.cuda.stream(ws):
-            ops.wgrad_direct(wide, narrow, *args, workspace=self.workspace_side, **kw)
+            yield self.workspace_side
         self._wgrad_pending = True
+
+    def _wgrad_direct(self, wide, narrow, *args, **kw):
+        """ops.wgrad_direct on the weight-gradient side stream."""
+        with self.side_stream(wide, narrow, *args, *kw.values()) as workspace:
+            ops.wgrad_direct(wide, narrow, *args, workspace=workspace, **kw)
 
     def record_side(self, *operands):
         """``record_stream(wgrad_stream)`` on every tensor among ``operands`` (the operands of a side-stream launch) that
@@ -656,22 +658,6 @@ class Engine:
         for t in operands:
             if isinstance(t, torch.Tensor) and t.untyped_storage().data_ptr() not in owned:
                 t.record_stream(ws)
-
-    def side_call(self, fn, *tensors):
-        """Run ``fn`` (small launches that only the optimiser step waits for) on the weight-gradient stream, behind
-        everything the current stream has issued so far; ``tensors`` are the buffers it reads."""
-        ws = self.wgrad_stream
-        if ws is None:
-            fn()
-            return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        ws.wait_event(ev)
-        for t in tensors:
-            t.record_stream(ws)
-        with torch.cuda.stream(ws):
-            fn()
-        self._wgrad_pending = True
 
     def defer_wgrad(self, x, dy, dw, db, post=None, zero=()):
         """``post``: called right behind the batched launch, on its stream (the image-side convs copy the real rows /
@@ -702,23 +688,11 @@ class Engine:
         if self.batch_wgrad and ops.wgrad_batch_eligible(x, dy, 3, PTI_CONV_S1, PTI_PRO_NONE):
             self.defer_wgrad(x, dy, dw, db, post, zero)
             return
-        ws = self.wgrad_stream
-        if ws is None:
+        with self.side_stream(x, dy, dw, db) as workspace:
             for t in zero:
                 t.zero_()
-            ops.conv_wgrad_mfma(x, dy, dw, db, accumulate=True, workspace=self.workspace)
+            ops.conv_wgrad_mfma(x, dy, dw, db, accumulate=True, workspace=workspace)
             post()
-            return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        ws.wait_event(ev)
-        self.record_side(x, dy, dw, db)
-        with torch.cuda.stream(ws):
-            for t in zero:
-                t.zero_()
-            ops.conv_wgrad_mfma(x, dy, dw, db, accumulate=True, workspace=self.workspace_side)
-            post()
-        self._wgrad_pending = True
 
     def flush_wgrad(self):
         """Launch the collected weight gradients (side stream if there is one), then hand the queued "gradients ready"
@@ -726,27 +700,13 @@ class Engine:
         jobs, self._wgrad_jobs = self._wgrad_jobs, []
         posts, self._wgrad_posts = self._wgrad_posts, []
         zero, self._wgrad_zero = self._wgrad_zero, ()
-        ws = self.wgrad_stream
         if jobs:
-            if ws is None:
+            with self.side_stream(*(t for job in jobs for t in job)) as workspace:
                 for t in zero:
                     t.zero_()
-                ops.conv_wgrad_mfma_batched(jobs, workspace=self.workspace)
+                ops.conv_wgrad_mfma_batched(jobs, workspace=workspace)
                 for p in posts:
                     p()
-            else:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream())
-                ws.wait_event(ev)
-                for job in jobs:
-                    self.record_side(*job)
-                with torch.cuda.stream(ws):
-                    for t in zero:
-                        t.zero_()
-                    ops.conv_wgrad_mfma_batched(jobs, workspace=self.workspace_side)
-                    for p in posts:
-                        p()
-                self._wgrad_pending = True
         queue, self._ready_queue = self._ready_queue, []
         for rng in queue:
             self._emit_ready(rng)
@@ -786,19 +746,12 @@ class Engine:
         cb = self.grad_ready_cb
         if cb is None:
             return
-        ws = self.wgrad_stream
-        if ws is None:
-            cb(*rng)
-            return
         # the block's gradients come from BOTH streams (weight gradients on the side stream, norm / bias / direct-conv
         # gradients on the main one): the side stream waits for the main stream up to here and the exchange is
-        # enqueued behind the side stream, so the data-gradient chain on the main stream is never held up
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        ws.wait_event(ev)
-        with torch.cuda.stream(ws):
+        # enqueued behind the side stream, so the data-gradient chain on the main stream is never held up.  No operands
+        # to record: the exchange works on the gradient arena
+        with self.side_stream():
             cb(*rng)
-        self._wgrad_pending = True
 
     # ---- encoder --------------------------------------------------------------------------------
     def encode_forward(self, x, save):
@@ -990,98 +943,58 @@ class Engine:
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for _, p in params)):
             return _EncodeFn.apply(self, x, *[p for _, p in params])
         if self.encode_graphs:
-            out = self._encode_graphed(x)
+            out = self._forward_graphed(self._enc_graphs, self.encode_forward, self.net.in_channels, "encode", x)
             if out is not None:
                 return out
         mu, sigma, _ = self.encode_forward(x, save=False)
         return mu, sigma
 
-    def _encode_graphed(self, x):
-        """Inference encode (no autograd) replayed from a HIP graph: the encoder forward is ~70 launches, and at the
-        batch sizes the regression / inference scripts use (reg_edente_from_dente.json: 8) the host needs longer to
-        enqueue them (~1.1 ms) than the GPU to run them.  One graph per input shape (at most four; further shapes run
-        eagerly), captured after an eager warm-up; dropped and re-captured when the weights were re-packed (the direct
-        convs' operands move).  Outputs are copies of the graph's static buffers.  PTI_ENCODE_GRAPH=0 turns it off."""
+    def _forward_graphed(self, graphs, forward, channels, what, x):
+        """Inference encode / decode (no autograd) replayed from a HIP graph: the encoder forward is ~70 launches, and at
+        the batch sizes the regression / inference scripts use (reg_edente_from_dente.json: 8) the host needs longer to
+        enqueue them (~1.1 ms) than the GPU to run them.  ``graphs``: ``_enc_graphs`` / ``_dec_graphs``, one graph per
+        input shape (at most four; further shapes run eagerly), captured after an eager warm-up; dropped and re-captured
+        when an operand buffer was re-allocated (``_drop_stale_graphs``).  ``forward``: ``encode_forward`` /
+        ``decode_forward``.  Returns copies of the graph's static output buffers as a tuple, or None when this call must
+        run eagerly.  PTI_ENCODE_GRAPH=0 turns it off."""
         if ops.KERNEL_PROFILE is not None:      # per-kernel timing wants the eager launches
             return None
-        x = self._check_input(x, self.net.in_channels, "encode")
+        x = self._check_input(x, channels, what)
         self.refresh_weights()
         self._drop_stale_graphs()
         key = tuple(x.shape)
-        ent = self._enc_graphs.get(key)
+        ent = graphs.get(key)
         if ent is None:
-            if len(self._enc_graphs) >= 4:
+            if len(graphs) >= 4:
                 return None
             sx = x.clone()
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream(device=self.dev)
             side.wait_stream(cur)
             with torch.cuda.stream(side):           # warm-up outside the capture (allocator, lazy state)
-                self.encode_forward(sx, save=False)
+                forward(sx, save=False)
             cur.wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            try:
-                # (thread_local: loader threads may issue copies meanwhile)
-                with gc_off_for_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    mu, sigma, _ = self.encode_forward(sx, save=False)
-            except Exception as ex:   # eager from here on
-                import warnings
-                warnings.warn(f"HIP-graph capture of the inference encode failed ({ex!r}); continuing with eager launches")
+            captured = capture_or_eager(f"the inference {what}", lambda: forward(sx, save=False)[:-1])
+            if captured is None:
                 self.encode_graphs = False
-                torch.cuda.synchronize()
                 return None
-            ent = self._enc_graphs[key] = (g, sx, mu, sigma)
-        g, sx, mu, sigma = ent
+            (g,), (outs,) = captured
+            ent = graphs[key] = (g, sx, outs)
+        g, sx, outs = ent
         sx.copy_(x)
         g.replay()
-        return mu.clone(), sigma.clone()
+        return tuple(o.clone() for o in outs)
 
     def decode(self, z):
         params = self._region_params(1)
         if torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for _, p in params)):
             return _DecodeFn.apply(self, z, *[p for _, p in params])
         if self.encode_graphs:
-            out = self._decode_graphed(z)
+            out = self._forward_graphed(self._dec_graphs, self.decode_forward, self.Lc, "decode", z)
             if out is not None:
-                return out
+                return out[0]
         recon, _ = self.decode_forward(z, save=False)
         return recon
-
-    def _decode_graphed(self, z):
-        """Inference decode replayed from a HIP graph per latent shape -- the mirror of ``_encode_graphed``."""
-        if ops.KERNEL_PROFILE is not None:
-            return None
-        z = self._check_input(z, self.Lc, "decode")
-        self.refresh_weights()
-        self._drop_stale_graphs()
-        key = tuple(z.shape)
-        ent = self._dec_graphs.get(key)
-        if ent is None:
-            if len(self._dec_graphs) >= 4:
-                return None
-            sz = z.clone()
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream(device=self.dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                self.decode_forward(sz, save=False)
-            cur.wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            try:
-                # (thread_local: loader threads may issue copies meanwhile)
-                with gc_off_for_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    recon, _ = self.decode_forward(sz, save=False)
-            except Exception as ex:   # eager from here on
-                import warnings
-                warnings.warn(f"HIP-graph capture of the inference decode failed ({ex!r}); continuing with eager launches")
-                self.encode_graphs = False
-                torch.cuda.synchronize()
-                return None
-            ent = self._dec_graphs[key] = (g, sz, recon)
-        g, sz, recon = ent
-        sz.copy_(z)
-        g.replay()
-        return recon.clone()
 
     def _prepare_grads(self, which):
         """Zero this region of the gradient arena unless the parameters' .grad already alias it (then

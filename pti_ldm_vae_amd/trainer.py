@@ -27,7 +27,7 @@ import torch
 
 from . import ops
 from .data_parallel import FlatGradAllReducer, broadcast_parameters
-from .engine import gc_off_for_capture
+from .engine import capture_or_eager
 from .optim import FlatAdam
 
 
@@ -315,6 +315,25 @@ class VAETrainer:
         self._plain_enc_bwd(carry)
         return out2
 
+    def _capture_inputs(self, images):
+        """Static inputs (gx, geps) of a step capture for this batch shape; None when this call must run eagerly: the
+        first two steps (they settle the lazily built state), more than four captured shapes, or per-kernel profiling."""
+        if self._eager_steps < 2 or len(self._graphs) >= 4 or ops.KERNEL_PROFILE is not None:
+            return None
+        net = self.net
+        down = 2 ** (len(net.channels) - 1)
+        gx = images.detach().float().contiguous().clone()
+        geps = torch.zeros(images.shape[0], net.latent_channels, images.shape[2] // down, images.shape[3] // down,
+                           dtype=torch.float32, device=images.device)
+        return gx, geps
+
+    def _fill_inputs(self, gx, geps, images, eps):
+        gx.copy_(images)
+        if eps is None:
+            geps.normal_(generator=self.gen)        # the same draws torch.randn(..., generator=self.gen) makes eagerly
+        else:
+            geps.copy_(eps)
+
     def _step_graphed(self, images, eps):
         """One plain step through a captured graph (see ``step_graph``); None when this call must run eagerly (the first
         two steps, which settle the lazily built state, and more than four batch shapes)."""
@@ -323,37 +342,24 @@ class VAETrainer:
                self.eng.wgrad_batch_max)
         st = self._graphs.get(key)
         if st is None:
-            if self._eager_steps < 2 or len(self._graphs) >= 4 or ops.KERNEL_PROFILE is not None:
+            inputs = self._capture_inputs(images)
+            if inputs is None:
                 return None
-            net = self.net
-            down = 2 ** (len(net.channels) - 1)
-            gx = images.detach().float().contiguous().clone()
-            geps = torch.zeros(images.shape[0], net.latent_channels, images.shape[2] // down, images.shape[3] // down,
-                               dtype=torch.float32, device=images.device)
+            gx, geps = inputs
             torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
             # the weight re-pack launches must be PART of the graph (every replay follows an optimiser step): if a
             # no_grad forward (validation, eval_losses) ran just before this call the packs are clean and
             # refresh_weights() would return early during capture -- every replay would then train on the weights as
             # last packed eagerly.  Force the dirty state for the capture.
             self.eng.packed_version = -1
-            try:
-                # (thread_local: loader threads may issue copies meanwhile)
-                with gc_off_for_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    out2 = self._plain_fwd_bwd(gx, geps)
-            except Exception as ex:   # a capture that fails must not take the run down: eager from here on
-                import warnings
-                warnings.warn(f"HIP-graph capture of the training step failed ({ex!r}); continuing with eager launches")
+            captured = capture_or_eager("the training step", lambda: self._plain_fwd_bwd(gx, geps))
+            if captured is None:
                 self.step_graph = False
-                torch.cuda.synchronize()
                 return None
+            (g,), (out2,) = captured
             st = self._graphs[key] = (g, gx, geps, out2)
         g, gx, geps, out2 = st
-        gx.copy_(images)
-        if eps is None:
-            geps.normal_(generator=self.gen)        # the same draws torch.randn(..., generator=self.gen) makes eagerly
-        else:
-            geps.copy_(eps)
+        self._fill_inputs(gx, geps, images, eps)
         g.replay()
         return out2.clone()
 
@@ -372,36 +378,23 @@ class VAETrainer:
                self.eng.wgrad_batch_max)
         st = self._graphs.get(key)
         if st is None:
-            if self._eager_steps < 2 or len(self._graphs) >= 4 or ops.KERNEL_PROFILE is not None:
+            inputs = self._capture_inputs(images)
+            if inputs is None:
                 return None
-            net = self.net
-            down = 2 ** (len(net.channels) - 1)
-            gx = images.detach().float().contiguous().clone()
-            geps = torch.zeros(images.shape[0], net.latent_channels, images.shape[2] // down, images.shape[3] // down,
-                               dtype=torch.float32, device=images.device)
+            gx, geps = inputs
             torch.cuda.synchronize()
-            ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             self.eng.packed_version = -1          # the re-pack launches are part of the first graph (see _step_graphed)
             self.eng.grad_ready_cb = None
-            try:
-                with gc_off_for_capture():
-                    with torch.cuda.graph(ga, capture_error_mode="thread_local"):
-                        out2, carry = self._plain_fwd_dec_bwd(gx, geps, join=True)
-                    with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
-                        self._plain_enc_bwd(carry)
-            except Exception as ex:
-                import warnings
-                warnings.warn(f"HIP-graph capture of the data-parallel step failed ({ex!r}); continuing with eager launches")
+            captured = capture_or_eager("the data-parallel step",
+                                        lambda: self._plain_fwd_dec_bwd(gx, geps, join=True),
+                                        lambda first: self._plain_enc_bwd(first[1]))
+            if captured is None:
                 self.step_graph = False
-                torch.cuda.synchronize()
                 return None
+            (ga, gb), ((out2, carry), _) = captured
             st = self._graphs[key] = (ga, gb, gx, geps, out2, carry)     # `carry` keeps the tensors crossing the seam alive
         ga, gb, gx, geps, out2, _ = st
-        gx.copy_(images)
-        if eps is None:
-            geps.normal_(generator=self.gen)
-        else:
-            geps.copy_(eps)
+        self._fill_inputs(gx, geps, images, eps)
         red = self.reducer
         (e_lo, e_hi), (d_lo, d_hi) = self.net.arena_regions()
         red.begin_step()

@@ -95,7 +95,7 @@ def test_regression_script_end_to_end_on_tiff_directory(dev, tmp_path):
 
 
 def test_inference_encode_graph_replay_equals_eager(dev):
-    """``encode_deterministic`` under no_grad replays a HIP graph per input shape (engine._encode_graphed): same bits as
+    """``encode_deterministic`` under no_grad replays a HIP graph per input shape (engine._forward_graphed): same bits as
     the eager launches, across repeated calls, a second shape, and a weight update (the graphs are dropped and
     re-captured when the packed operands change)."""
     from pti_ldm_vae_amd.models import VAEModel

@@ -13,12 +13,15 @@ stay green while the protocol is broken.  This module checks the protocol itself
     depend on timing (single GPU: no gradient exchange is attached, so ``Engine._emit_ready`` issues nothing there);
   * the lagging side stream (``test_lagging_side_stream_is_bitwise_the_single_stream_step``): each side-stream launch is
     preceded by a GPU sleep there, and five steps must give the same bits as the single-stream layout;
+  * the side stream switched off for one step and back on (``test_side_stream_switched_off_and_on_between_steps``): the
+    engine looks the stream up at every launch, and the bits do not change;
   * the native trainer at 2..8 image channels (the image-side convs run on zero-padded MFMA tiles and their padded weight
     gradients ride the side stream) against the CPU oracle and against the direct kernels (``PTI_IMG_MFMA=0``).
 """
 import functools
 import inspect
 import os
+import types
 import warnings
 
 import pytest
@@ -340,6 +343,57 @@ def test_lagging_side_stream_is_bitwise_the_single_stream_step(dev, monkeypatch,
     for i, (a, b) in enumerate(zip(g1, g0)):
         assert torch.equal(a, b), f"step {i + 1}: gradient arena differs, max |diff| {(a - b).abs().max().item():.3e}"
     assert torch.equal(p1, p0), f"parameters differ, max |diff| {(p1 - p0).abs().max().item():.3e}"
+
+
+def test_side_stream_switched_off_and_on_between_steps(dev, monkeypatch):
+    """``Engine.wgrad_stream`` is looked up at every launch, not cached: a trainer whose side stream is taken away for its
+    second step (``eng.wgrad_stream = None``, as the benchmark's host-enqueue measurement does between steps) and given
+    back for the third gives the same losses, the same gradient arena after every step and the same final parameters, bit
+    for bit, as a trainer that keeps the side stream throughout (the two layouts are bitwise equal:
+    test_lagging_side_stream_is_bitwise_the_single_stream_step).  And the switch is honoured: in the second step no
+    weight-gradient launch runs on the stored side stream, in the third at least one does again."""
+    from pti_ldm_vae_amd import ops
+    from pti_ldm_vae_amd.trainer import VAETrainer
+    cfg, batch, env = CASES["A1"]
+    _set_env(monkeypatch, env)
+    xs, epss = _inputs(cfg, batch, steps=3)
+    stored = types.SimpleNamespace(wgrad_stream=None)     # what _on_side looks at: the stream, also while the engine has none
+    on_side = [0, 0, 0]                                   # SIDE_OPS launches on the stored stream, per step
+    step = [0]
+
+    def counted(fn):
+        def wrapped(*args, **kw):
+            on_side[step[0]] += _on_side(stored)
+            return fn(*args, **kw)
+        return wrapped
+    for name in SIDE_OPS:
+        monkeypatch.setattr(ops, name, counted(getattr(ops, name)))
+    runs = []
+    for toggled in (False, True):
+        model = _model(cfg, dev)
+        tr = VAETrainer(model, lr=1e-3)
+        tr.step_graph = False
+        stored.wgrad_stream = tr.eng.wgrad_stream
+        assert stored.wgrad_stream is not None
+        on_side[:] = [0, 0, 0]
+        losses, grads = [], []
+        for i, (x, eps) in enumerate(zip(xs, epss)):
+            step[0] = i
+            tr.eng.wgrad_stream = None if (toggled and i == 1) else stored.wgrad_stream
+            losses.append(tr.step(x.to(dev), eps.to(dev))["loss"])
+            grads.append(model.autoencoder.grad_arena.clone())
+        torch.cuda.synchronize()
+        assert not tr._graphs
+        runs.append(([l.item() for l in losses], grads, model.autoencoder.param_arena.clone(), list(on_side)))
+        del tr, model
+    (l1, g1, p1, n1), (l2, g2, p2, n2) = runs
+    print(f"side-stream launches per step: kept {n1}, switched off for step 2 {n2}")
+    assert min(n1) >= 1, n1
+    assert n2[1] == 0 and n2[0] >= 1 and n2[2] >= 1, n2
+    assert l2 == l1, (l2, l1)
+    for i, (a, b) in enumerate(zip(g2, g1)):
+        assert torch.equal(a, b), f"step {i + 1}: gradient arena differs, max |diff| {(a - b).abs().max().item():.3e}"
+    assert torch.equal(p2, p1), f"parameters differ, max |diff| {(p2 - p1).abs().max().item():.3e}"
 
 
 # =====================================================================================================================
