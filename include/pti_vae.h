@@ -32,7 +32,8 @@ typedef void* pti_stream_t; /* hipStream_t */
                                  pti_conv2d_mfma_gnbwd_chain (+ _supported), pti_gn_affine_grads, pti_gn_sums_finalize_affine
                                Still 5: pti_image_metrics / pti_image_metrics_ws_floats, and after them pti_latent_pairwise /
                                pti_latent_group_stats (+ their _ws_floats), were APPENDED (no existing entry point, structure
-                               or constant changed), so a caller built against the earlier 5 keeps working. */
+                               or constant changed), so a caller built against the earlier 5 keeps working.  The same holds
+                               for pti_mask_geometry, appended after those. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -486,6 +487,28 @@ int pti_latent_pairwise(const float* a, int64_t lda, int n1, const float* b, int
 int64_t pti_latent_group_stats_ws_floats(int n1, int n2, int patients, int d);
 int pti_latent_group_stats(const float* a, int64_t lda, int n1, const int32_t* seg_a, const float* b, int64_t ldb, int n2,
                            const int32_t* seg_b, int patients, int d, float* out_e4, float* workspace, pti_stream_t s);
+
+/* ---- mask geometry (reference vae_scripts/compute_mask_metrics.py:38-68,176-193; csrc/mask_geometry.hip) ----
+ * The per-pixel work behind the AR-VAE attribute files, for a batch of binary masks of mixed size in ONE launch (one
+ * workgroup per image, no atomics, no workspace: integer results, bitwise reproducible, independent of batch position).
+ *   src: the masks concatenated in their stored type -- elem 0 = uint8, 1 = uint16, 2 = float32; offsets[i]: ELEMENT
+ *        offset of image i (any value: rows need no alignment beyond src's own, a multiple of the element size);
+ *        hw[i] = {H, W}.  offsets / hw are device arrays, as for pti_preprocess_batch.
+ *   foreground: integers != 0 (unsigned, the whole word); float32 by bit pattern, 0 < (int32) bits <= 0x7f800000, which is
+ *        IEEE x > 0 whatever the denormal mode (NaN, -0.0, negatives: background; subnormals, +inf: foreground).
+ *   bbox_b4[i] = {x0, y0, w, h} of all foreground pixels; {-1, -1, 0, 0} for a mask without any (its widths are all 0).
+ *   The width of a row is last foreground column - first + 1 over the WHOLE row (gaps count), 0 for an empty row.
+ *   bbox_widths[i][k], k < samples: width of row y0 + sample_rows[h * samples + k], where sample_rows is a device table
+ *        int32 [max_h + 1][samples] built by the caller (the reference's np.linspace(0, h, samples + 2, dtype=int)
+ *        truncates a float64 product and is not i*h/(samples+1): the host tabulates it, the kernel only looks it up);
+ *        an entry that leaves the image gives width 0.
+ *   bottom_widths[i][k], k < n_bottom: width of row clamp(H - 1 - bottom_offsets[k], 0, H - 1) (device array of offsets).
+ *   samples == 0 / n_bottom == 0 are legal and the matching pointers may then be NULL.
+ *   max_h: the caller's bound on every H, at most 4096 (the kernel keeps one {first, last} pair per row in LDS; above
+ *        that PTI_EUNSUPPORTED).  An image with H > max_h, H < 1 or W < 1 is not read: bbox {-2, -2, 0, 0}, widths 0. */
+int pti_mask_geometry(const void* src, const int64_t* offsets, const int32_t* hw, int b, int elem, int max_h,
+                      const int32_t* sample_rows, int samples, const int32_t* bottom_offsets, int n_bottom,
+                      int32_t* bbox_b4, int32_t* bbox_widths, int32_t* bottom_widths, pti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,7 @@ SIGNATURES = {
     "pti_latent_pairwise": (_I, [_P, _I64, _I, _P, _I64, _I, _I, _P, _I, _P, _I64, _P, _P]),
     "pti_latent_group_stats_ws_floats": (_I64, [_I, _I, _I, _I]),
     "pti_latent_group_stats": (_I, [_P, _I64, _I, _P, _P, _I64, _I, _P, _I, _I, _P, _P, _P]),
+    "pti_mask_geometry": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -919,6 +919,68 @@ def latent_group_stats(a, seg_a, b, seg_b, *, out=None):
     return out
 
 
+# ---- mask geometry (csrc/mask_geometry.hip; include/pti_vae.h "mask geometry") -----------------------------------------
+MASK_DTYPES = (torch.uint8, torch.uint16, F32)   # dtype of the mask buffer for `elem` 0, 1, 2 of pti_mask_geometry
+MASK_ROW_CAP = 4096                                     # the kernel's bound on max_h
+
+
+def mask_geometry(src, offsets, hw, *, elem, max_h, sample_rows, bottom_offsets, out=None):
+    """Bounding box and row widths of a batch of binary masks of mixed size in one launch (``pti_mask_geometry``) ->
+    ``(bbox [b, 4], bbox_widths [b, samples], bottom_widths [b, n_bottom])`` as int32 device tensors.
+
+    ``src``: the masks concatenated in their stored type, a flat uint8 / uint16 / float32 device tensor whose dtype
+    matches ``elem`` (0 / 1 / 2); ``offsets`` int64 [b]: element offset of every image (no alignment needed); ``hw``
+    int32 [b, 2].  ``sample_rows`` int32 [max_h + 1, samples]: for every bounding-box height the rows, relative to the
+    box's first row, whose widths are wanted (``data.mask_metrics.sample_row_table``); ``bottom_offsets`` int32
+    [n_bottom]: rows counted up from the image's last row, clamped per image.  Either may have zero entries.
+    ``bbox`` is ``{x0, y0, w, h}``, ``{-1, -1, 0, 0}`` for a mask without foreground and ``{-2, -2, 0, 0}`` for an image
+    whose height exceeds ``max_h`` (it is not read).  ``out``: the three int32 tensors to write instead of new ones.
+    Runs on the current stream, no host sync."""
+    if elem not in (0, 1, 2):
+        raise ValueError(f"mask_geometry: elem must be 0 (uint8), 1 (uint16) or 2 (float32), got {elem!r}")
+    wanted = (("src", src, MASK_DTYPES[elem]), ("offsets", offsets, I64), ("hw", hw, torch.int32),
+              ("sample_rows", sample_rows, torch.int32), ("bottom_offsets", bottom_offsets, torch.int32))
+    for name, t, dtype in wanted:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise TypeError(f"mask_geometry: {name} must be a {dtype} tensor" + (f" for elem {elem}" if name == "src" else "")
+                            + f", got {getattr(t, 'dtype', type(t))}")
+    for name, t, _ in wanted:
+        if not t.is_cuda or t.device != src.device:
+            raise ValueError(f"mask_geometry: {name} must be a CUDA(HIP) tensor on the device of src")
+        if not t.is_contiguous():
+            raise ValueError(f"mask_geometry: {name} must be contiguous")
+    b = offsets.numel()
+    if src.dim() != 1 or offsets.dim() != 1 or b < 1 or tuple(hw.shape) != (b, 2):
+        raise ValueError("mask_geometry: src must be flat, offsets [b] with b >= 1 and hw [b, 2]")
+    max_h = int(max_h)
+    if not 0 <= max_h <= MASK_ROW_CAP:
+        raise ValueError(f"mask_geometry: max_h must be in [0, {MASK_ROW_CAP}], got {max_h}")
+    if sample_rows.dim() != 2 or sample_rows.shape[0] != max_h + 1:
+        raise ValueError(f"mask_geometry: sample_rows must be [max_h + 1, samples] = [{max_h + 1}, samples], "
+                         f"got {tuple(sample_rows.shape)}")
+    if bottom_offsets.dim() != 1:
+        raise ValueError(f"mask_geometry: bottom_offsets must be a vector, got {tuple(bottom_offsets.shape)}")
+    samples, n_bottom = sample_rows.shape[1], bottom_offsets.numel()
+    shapes = ((b, 4), (b, samples), (b, n_bottom))
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=torch.int32, device=src.device) for sh in shapes)
+    else:   # caller-owned outputs (views of larger buffers included)
+        if len(out) != 3:
+            raise ValueError("mask_geometry: out must be (bbox, bbox_widths, bottom_widths)")
+        for name, t, sh in zip(("bbox", "bbox_widths", "bottom_widths"), out, shapes):
+            _chk(t, torch.int32, f"mask_geometry: out {name}")
+            if tuple(t.shape) != sh or t.device != src.device:
+                raise ValueError(f"mask_geometry: out {name} must be {list(sh)} on {src.device}")
+    bbox, bbox_widths, bottom_widths = out
+    # a table or an output without entries is passed as NULL
+    L.check(L.lib().pti_mask_geometry(_ptr(src), _ptr(offsets), _ptr(hw), b, elem, max_h,
+                                      _ptr(sample_rows) if samples else None, samples,
+                                      _ptr(bottom_offsets) if n_bottom else None, n_bottom, _ptr(bbox),
+                                      _ptr(bbox_widths) if samples else None, _ptr(bottom_widths) if n_bottom else None,
+                                      _stream()), "pti_mask_geometry")
+    return bbox, bbox_widths, bottom_widths
+
+
 # ---- PatchDiscriminator passes (csrc/discriminator.hip; include/pti_vae.h "PatchDiscriminator") -----------------------
 def pd_out_hw(h, w, stride):
     return (h + 2 - 4) // stride + 1, (w + 2 - 4) // stride + 1
