@@ -33,7 +33,9 @@ typedef void* pti_stream_t; /* hipStream_t */
                                Still 5: pti_image_metrics / pti_image_metrics_ws_floats, and after them pti_latent_pairwise /
                                pti_latent_group_stats (+ their _ws_floats), were APPENDED (no existing entry point, structure
                                or constant changed), so a caller built against the earlier 5 keeps working.  The same holds
-                               for pti_mask_geometry, appended after those. */
+                               for pti_mask_geometry, appended after those.
+                               Still 5: pti_mlp_head_fwd / pti_mlp_head_ws_floats / pti_regression_metrics, appended after
+                               pti_mask_geometry in the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -509,6 +511,38 @@ int pti_latent_group_stats(const float* a, int64_t lda, int n1, const int32_t* s
 int pti_mask_geometry(const void* src, const int64_t* offsets, const int32_t* hw, int b, int elem, int max_h,
                       const int32_t* sample_rows, int samples, const int32_t* bottom_offsets, int n_bottom,
                       int32_t* bbox_b4, int32_t* bbox_widths, int32_t* bottom_widths, pti_stream_t s);
+
+/* ---- regression head, evaluation side (reference src/pti_ldm_vae/models/regression_head.py:30-78,
+ *      src/pti_ldm_vae/utils/regression_utils.py:350-388, src/pti_ldm_vae/utils/metrics.py:6-37; csrc/regression_head.hip) ----
+ * pti_mlp_head_fwd: forward of LatentRegressor in eval mode (dropout = identity) fused with the target de-normalisation
+ *   and the per-row loss, two launches, no atomics.
+ *   x: fp32 [n][d] with a row stride ldx >= d in ELEMENTS (torch.flatten(mu_nchw, 1)); params: ONE fp32 device buffer
+ *   W0, b0, W1, b1, ... in nn.Linear layout ([out][in] row-major); dims: HOST array of n_layers + 1 widths, dims[0] == d.
+ *   act between the layers: 0 relu, 1 gelu (exact erf form), 2 leaky_relu (slope 0.01), 3 elu (alpha 1).
+ *   mean / std: fp32 [T] device arrays, both NULL or both set (a zero std was replaced on the host); targets: fp32 [n][T]
+ *   or NULL; loss_kind: 0 MSE, 1 SmoothL1 (beta 1).
+ *   pred[n][T] = out * std + mean (out without a normaliser); with targets rowloss[n] = sum_t l(out_t, (target_t - mean_t) /
+ *   std_t), the loss on the NORMALISED scale as validate_one_epoch takes it (rowloss may be NULL without targets).
+ *   Limits: 1 <= n_layers <= PTI_MLP_MAX_LAYERS, hidden widths <= PTI_MLP_MAX_WIDTH, T <= PTI_MLP_MAX_OUT, any d, n >= 1
+ *   (up to 2^24); beyond them PTI_EUNSUPPORTED, NULL pointers / dimensions < 1 PTI_EINVAL, both before any launch.
+ *   The sum over d has one order that depends on d only (fmaf chains over 512-column slabs in ascending k, slab sums added
+ *   in ascending order); with few rows and a long d the slabs are split over workgroups and folded in the same order, so
+ *   both routes give the same bits and row i of pred / rowloss depends on row i only (not on n, its position, the route).
+ *   workspace: pti_mlp_head_ws_floats(n, d, dims, n_layers) floats (pure host arithmetic; 0 = unsupported shape).
+ * pti_regression_metrics: one fixed-order fp64 fold over a whole evaluation set, pred / targets fp32 [n][t], rowloss [n]:
+ *   out[0] = mean over the consecutive chunks of `batch` rows (the last may be short) of sum(rowloss) / (rows * t) -- the
+ *   mean of per-batch loss means that validate_one_epoch returns, not the global mean; out[1 .. t] MAE per target,
+ *   out[t+1 .. 2t] MSE per target, out[2t+1] / out[2t+2] their means over the targets (compute_regression_metrics).
+ *   out: 2t + 3 doubles on the device; t <= PTI_MLP_MAX_OUT.                                                            */
+#define PTI_MLP_MAX_LAYERS 8
+#define PTI_MLP_MAX_WIDTH 1024
+#define PTI_MLP_MAX_OUT 64
+int64_t pti_mlp_head_ws_floats(int n, int d, const int32_t* dims, int n_layers);
+int pti_mlp_head_fwd(const float* x, int64_t ldx, int n, int d, const float* params, const int32_t* dims, int n_layers,
+                     int act, const float* mean, const float* std, const float* targets, int loss_kind, float* pred,
+                     float* rowloss, float* workspace, pti_stream_t s);
+int pti_regression_metrics(const float* pred, const float* targets, const float* rowloss, int n, int t, int batch,
+                           double* out, pti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,9 @@ SIGNATURES = {
     "pti_latent_group_stats_ws_floats": (_I64, [_I, _I, _I, _I]),
     "pti_latent_group_stats": (_I, [_P, _I64, _I, _P, _P, _I64, _I, _P, _I, _I, _P, _P, _P]),
     "pti_mask_geometry": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "pti_mlp_head_ws_floats": (_I64, [_I, _I, C.POINTER(C.c_int32), _I]),
+    "pti_mlp_head_fwd": (_I, [_P, _I64, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "pti_regression_metrics": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

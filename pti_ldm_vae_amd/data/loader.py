@@ -270,3 +270,30 @@ def create_regression_dataloaders(data_base_dir: str, attributes_path, targets: 
     val = DeviceImageLoader(val_paths, batch_size, patch_size, device, shuffle=False, seed=s, num_workers=num_workers,
                             attributes=va_attrs, target_names=list(targets))
     return train, val, train_paths, val_paths
+
+
+def create_regression_eval_dataloader(input_dir: str, attributes_path, targets: list[str], patch_size: tuple[int, int],
+                                      batch_size: int, num_workers: int = 4, num_samples: int | None = None,
+                                      data_source: str = "edente", normalize_attributes: dict | None = None, device="cuda"):
+    """The reference's ``create_regression_eval_dataloader`` (dataloaders.py:725-778) on the device input pipeline:
+    ``(loader, paths)`` over the sorted images of ``input_dir`` (capped to the first ``num_samples``), no shuffling, the
+    short last batch kept; batches are ``(images [b,1,Hp,Wp], targets [b,T])`` device tensors in ``targets`` order."""
+    from .attributes import filter_attributes_for_paths, select_attribute_sources
+    if len(targets) == 0:
+        raise ValueError("targets must contain at least one entry.")
+    paths = list_tif_paths(input_dir, data_source)
+    if num_samples is not None:
+        paths = paths[:num_samples]
+    sources = select_attribute_sources(attributes_path, data_source)
+    attrs = filter_attributes_for_paths(paths, sources, {t: t for t in targets}, normalize_attributes)
+    loader = DeviceImageLoader(paths, batch_size, patch_size, device, shuffle=False, num_workers=num_workers,
+                               attributes=attrs, target_names=list(targets))
+    return loader, paths
+
+
+def create_regression_inference_dataloader(input_dir: str, patch_size: tuple[int, int], batch_size: int,
+                                           num_samples: int | None = None, num_workers: int = 4, device="cuda"):
+    """The reference's ``create_regression_inference_dataloader`` (dataloaders.py:781-795): images only, exactly
+    ``create_vae_inference_dataloader``."""
+    return create_vae_inference_dataloader(input_dir=input_dir, patch_size=patch_size, batch_size=batch_size,
+                                           num_samples=num_samples, num_workers=num_workers, device=device)

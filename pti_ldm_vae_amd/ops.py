@@ -1333,3 +1333,148 @@ def squeeze_conv1_bwd(g, t0, w10, h, w):
     dx = torch.empty(n, 1, h, w, dtype=F32, device=g.device)
     L.check(L.lib().pti_squeeze_conv1_bwd(_ptr(g), _ptr(t0), _ptr(w10), _ptr(dx), n, h, w, _stream()), "pti_squeeze_conv1_bwd")
     return dx
+
+
+# ---- regression head, evaluation side (csrc/regression_head.hip; include/pti_vae.h "regression head") -----------------
+MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_OUT = 8, 1024, 64    # PTI_MLP_MAX_* of include/pti_vae.h
+MLP_ACTS = ("relu", "gelu", "leaky_relu", "elu")            # activation codes 0 .. 3 of pti_mlp_head_fwd
+MLP_LOSSES = {"mse": 0, "mse_loss": 0, "smooth_l1": 1, "huber": 1}
+_mlp_ws = {}
+
+
+def mlp_head_pack(regressor):
+    """``LatentRegressor`` -> ``(params, dims, act)``: one flat fp32 tensor ``W0, b0, W1, b1, ...`` (``nn.Linear`` layout)
+    on the head's device, the layer widths ``[in, hidden..., out]`` and the activation's code (0 when there is no hidden
+    layer).  Dropout layers are skipped: the kernel is the eval-mode forward."""
+    from torch import nn
+    kinds = {nn.ReLU: 0, nn.GELU: 1, nn.LeakyReLU: 2, nn.ELU: 3}
+    linears, acts = [], set()
+    for m in regressor.mlp:
+        if isinstance(m, nn.Linear):
+            linears.append(m)
+        elif type(m) in kinds:
+            acts.add(kinds[type(m)])
+        elif not isinstance(m, nn.Dropout):
+            raise TypeError(f"mlp_head_pack: unsupported layer {type(m).__name__}")
+    if not linears or len(acts) > 1:
+        raise ValueError("mlp_head_pack: expected nn.Linear layers with one kind of activation between them")
+    for m in regressor.mlp:
+        if isinstance(m, nn.GELU) and getattr(m, "approximate", "none") != "none":
+            raise ValueError("mlp_head_pack: only the exact (erf) GELU is built")
+        if isinstance(m, nn.LeakyReLU) and m.negative_slope != 0.01 or isinstance(m, nn.ELU) and m.alpha != 1.0:
+            raise ValueError("mlp_head_pack: only LeakyReLU(0.01) / ELU(1.0) are built")
+    dims = [linears[0].in_features] + [m.out_features for m in linears]
+    for a, b in zip(linears[:-1], linears[1:]):
+        if b.in_features != a.out_features:
+            raise ValueError("mlp_head_pack: layer widths do not chain")
+    if any(m.bias is None for m in linears):
+        raise ValueError("mlp_head_pack: every nn.Linear must have a bias")
+    with torch.no_grad():
+        params = torch.cat([t.detach().to(F32).reshape(-1) for m in linears for t in (m.weight, m.bias)]).contiguous()
+    return params, dims, (acts.pop() if acts else 0)
+
+
+def mlp_head_supported(dims) -> bool:
+    """Whether ``pti_mlp_head_fwd`` is built for these layer widths ``[in, hidden..., out]``."""
+    dims = [int(v) for v in dims]
+    return (2 <= len(dims) <= MLP_MAX_LAYERS + 1 and all(v >= 1 for v in dims) and dims[-1] <= MLP_MAX_OUT
+            and all(v <= MLP_MAX_WIDTH for v in dims[1:-1]))
+
+
+def mlp_head_route(n, d, h1) -> str:
+    """The route ``pti_mlp_head_fwd`` takes for ``n`` rows of ``d`` columns into a first layer of ``h1`` units (pure host
+    arithmetic, the library's own rule): ``"split"`` -- at most 16 (16-row tile, 64-unit block) workgroups and more than
+    one 512-column slab: the slabs are spread over workgroups and folded by the tail -- else ``"direct"``.  The route
+    never changes a result bit."""
+    slabs = -(-int(d) // 512)
+    wgs = -(-int(n) // 16) * -(-int(h1) // 64)
+    return "split" if slabs > 1 and wgs <= 16 and slabs * int(n) * int(h1) <= 1 << 26 else "direct"
+
+
+def _dims_array(dims):
+    return (C.c_int32 * len(dims))(*[int(v) for v in dims])
+
+
+def mlp_head_fwd(x, params, dims, act, *, mean=None, std=None, targets=None, loss="mse", pred=None, rowloss=None):
+    """Eval-mode forward of the regression head on ``x`` [n, d] (``torch.flatten(mu, 1)``; a row-strided view is used in
+    place) with the packed ``params`` / ``dims`` / ``act`` of ``mlp_head_pack`` -> ``(pred [n, T], rowloss [n] or None)``.
+    ``pred = out * std + mean`` when the normaliser's ``mean`` / ``std`` [T] are given; with ``targets`` [n, T]
+    ``rowloss[i] = sum_t loss(out[i, t], (targets[i, t] - mean[t]) / std[t])`` (``loss``: "mse" or "smooth_l1"), the loss
+    on the normalised scale.  Row ``i`` of both depends on row ``i`` only, bit for bit.  Runs on the current stream, no
+    host sync; the scratch buffer is cached per (stream, shape).  An unsupported head (``mlp_head_supported``) raises."""
+    x = _rows(x, "mlp_head_fwd: x")
+    n, d = x.shape
+    dims = [int(v) for v in dims]
+    if len(dims) < 2 or dims[0] != d:
+        raise ValueError(f"mlp_head_fwd: dims {dims} do not start with the {d} columns of x")
+    if not mlp_head_supported(dims):
+        raise ValueError(f"mlp_head_fwd: unsupported head {dims} (at most {MLP_MAX_LAYERS} layers, hidden widths <= "
+                         f"{MLP_MAX_WIDTH}, outputs <= {MLP_MAX_OUT}); there is no silent fallback")
+    if loss not in MLP_LOSSES:
+        raise ValueError(f"mlp_head_fwd: loss must be one of {sorted(MLP_LOSSES)}, got {loss!r}")
+    if not 0 <= int(act) < len(MLP_ACTS):
+        raise ValueError(f"mlp_head_fwd: activation code {act!r}")
+    t_out = dims[-1]
+    _chk(params, F32, "mlp_head_fwd: params", 1)
+    if params.numel() != sum(a * b + b for a, b in zip(dims[:-1], dims[1:])) or params.device != x.device:
+        raise ValueError(f"mlp_head_fwd: params must hold the weights and biases of {dims} on {x.device}")
+    if (mean is None) != (std is None):
+        raise ValueError("mlp_head_fwd: mean and std go together")
+    vecs = []
+    for name, v in (("mean", mean), ("std", std)):
+        if v is not None:
+            if not isinstance(v, torch.Tensor) or v.numel() != t_out:
+                raise ValueError(f"mlp_head_fwd: {name} must hold {t_out} values")
+            v = v.to(device=x.device, dtype=F32).reshape(-1).contiguous()
+        vecs.append(v)
+    mean, std = vecs
+    if targets is not None:
+        _chk(targets, F32, "mlp_head_fwd: targets", 2)
+        if tuple(targets.shape) != (n, t_out) or targets.device != x.device:
+            raise ValueError(f"mlp_head_fwd: targets must be [{n}, {t_out}] on {x.device}")
+    if pred is None:
+        pred = torch.empty(n, t_out, dtype=F32, device=x.device)
+    else:
+        _chk(pred, F32, "mlp_head_fwd: pred", 2)
+        if tuple(pred.shape) != (n, t_out) or pred.device != x.device:
+            raise ValueError(f"mlp_head_fwd: pred must be [{n}, {t_out}] on {x.device}")
+    if targets is None:
+        rowloss = None
+    elif rowloss is None:
+        rowloss = torch.empty(n, dtype=F32, device=x.device)
+    else:
+        _chk(rowloss, F32, "mlp_head_fwd: rowloss", 1)
+        if rowloss.numel() != n or rowloss.device != x.device:
+            raise ValueError(f"mlp_head_fwd: rowloss must be [{n}] on {x.device}")
+    arr = _dims_array(dims)
+    floats = L.lib().pti_mlp_head_ws_floats(n, d, arr, len(dims) - 1)
+    if floats <= 0:
+        raise ValueError(f"mlp_head_fwd: unsupported shape x {tuple(x.shape)} head {dims}")
+    stream = _stream()
+    key = (x.device.index, stream, n, d, dims[1])
+    ws = _mlp_ws.get(key)
+    if ws is None:
+        ws = _mlp_ws[key] = torch.empty(floats, dtype=F32, device=x.device)
+    L.check(L.lib().pti_mlp_head_fwd(_ptr(x), x.stride(0), n, d, _ptr(params), arr, len(dims) - 1, int(act), _ptr(mean),
+                                     _ptr(std), _ptr(targets), MLP_LOSSES[loss], _ptr(pred), _ptr(rowloss), _ptr(ws), stream),
+            "pti_mlp_head_fwd")
+    return pred, rowloss
+
+
+def regression_metrics(pred, targets, rowloss, batch):
+    """One fixed-order fp64 fold over a whole evaluation set (``pti_regression_metrics``): ``pred`` / ``targets`` fp32
+    [n, T], ``rowloss`` fp32 [n] (``mlp_head_fwd``) -> fp64 device tensor ``[2T + 3]``: the mean over consecutive chunks of
+    ``batch`` rows of ``sum(rowloss) / (rows * T)`` (``validate_one_epoch``'s mean of batch means), MAE per target, MSE per
+    target, and the means of the two over the targets.  Runs on the current stream, no host sync."""
+    _chk(pred, F32, "regression_metrics: pred", 2)
+    _chk(targets, F32, "regression_metrics: targets", 2)
+    _chk(rowloss, F32, "regression_metrics: rowloss", 1)
+    n, t = pred.shape
+    if n < 1 or not 1 <= t <= MLP_MAX_OUT or int(batch) < 1:
+        raise ValueError(f"regression_metrics: need n >= 1, 1 <= T <= {MLP_MAX_OUT} and batch >= 1, got {n}, {t}, {batch}")
+    if targets.shape != pred.shape or rowloss.numel() != n or targets.device != pred.device or rowloss.device != pred.device:
+        raise ValueError("regression_metrics: pred / targets [n, T] and rowloss [n] must agree in shape and device")
+    out = torch.empty(2 * t + 3, dtype=torch.float64, device=pred.device)
+    L.check(L.lib().pti_regression_metrics(_ptr(pred), _ptr(targets), _ptr(rowloss), n, t, int(batch), _ptr(out), _stream()),
+            "pti_regression_metrics")
+    return out

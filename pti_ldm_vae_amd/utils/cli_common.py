@@ -68,3 +68,22 @@ def resolve_eval_output_dir(config_file: str, output_dir: str | None) -> Path:
     out = Path(output_dir) if output_dir is not None else default_eval_output_dir(config_file)
     out.mkdir(parents=True, exist_ok=True)
     return out
+
+
+def load_json_config(config_file: str) -> dict[str, Any]:
+    """The parsed JSON configuration file (reference cli_common.py:137-147)."""
+    import json
+    with open(config_file, encoding="utf-8") as handle:
+        return json.load(handle)
+
+
+def resolve_run_dir(config: dict[str, Any], config_file: str) -> Path:
+    """-> ``config["run_dir"]``, or ``runs/<config stem>`` (stored back into ``config``) when it is missing; created
+    (reference cli_common.py:150-166)."""
+    if config.get("run_dir"):
+        run_dir = Path(config["run_dir"])
+    else:
+        run_dir = Path("runs") / Path(config_file).stem
+        config["run_dir"] = str(run_dir)
+    run_dir.mkdir(parents=True, exist_ok=True)
+    return run_dir

@@ -220,3 +220,82 @@ def build_regression_model_from_config(config: dict[str, Any], targets: list[str
     vae_cfg = load_vae_config(config["vae"]["config_file"])
     vae = load_vae_model(vae_cfg, config["vae"]["checkpoint"], device)
     return build_regression_model(vae, config, targets, device)
+
+
+# ---- evaluation / inference with the fused HIP head (csrc/regression_head.hip) -------------------------------------------
+def _normalizer_vectors(normalizer: TargetNormalizer | None, device: torch.device):
+    if normalizer is None:
+        return None, None
+    return (normalizer.mean.to(device=device, dtype=torch.float32).contiguous(),
+            normalizer.std.to(device=device, dtype=torch.float32).contiguous())
+
+
+def _packed_head(model: nn.Module):
+    """-> (params, dims, act) of ``model.regressor`` when the HIP head is built for it, else None (one line is printed)."""
+    from .. import ops
+    params, dims, act = ops.mlp_head_pack(model.regressor)
+    if not ops.mlp_head_supported(dims):
+        print(f"[INFO] regression head {dims} is outside the HIP kernel's limits: using the torch head")
+        return None
+    return params, dims, act
+
+
+def predict_on_device(model: nn.Module, dataloader, normalizer: TargetNormalizer | None) -> torch.Tensor:
+    """De-normalised predictions ``[N, T]`` of the whole set, kept on the device (no host sync): per batch the frozen
+    encoder under ``no_grad``, then ONE fused head forward (``ops.mlp_head_fwd``).  ``dataloader`` yields images, or
+    ``(images, targets)`` pairs whose targets are ignored."""
+    from .. import ops
+    model.eval()
+    device = next(model.regressor.parameters()).device
+    packed = _packed_head(model)
+    mean, std = _normalizer_vectors(normalizer, device)
+    preds = []
+    with torch.no_grad():
+        for batch in dataloader:
+            images = (batch[0] if isinstance(batch, (tuple, list)) else batch).to(device, non_blocking=True)
+            if packed is None:
+                out = model(images)
+                preds.append(normalizer.denormalize(out) if normalizer is not None else out)
+                continue
+            flat = torch.flatten(model.vae.encode_deterministic(images), start_dim=1)
+            preds.append(ops.mlp_head_fwd(flat, *packed, mean=mean, std=std)[0])
+    if not preds:
+        raise RuntimeError("Inference dataloader produced zero batches.")
+    return torch.cat(preds)
+
+
+def evaluate_on_device(model: nn.Module, dataloader, loss_name: str, target_names: list[str],
+                       normalizer: TargetNormalizer | None, batch_size: int) -> tuple[float, dict[str, float]]:
+    """``validate_one_epoch`` with the fused HIP head: same return value ``(val_loss, metrics)`` with the same keys and
+    meaning -- the mean over the batches of the batch-mean loss on (normalised) targets, MAE / MSE of the de-normalised
+    predictions per target and averaged.  Per batch: encoder, one fused head forward writing ``pred`` and the per-row
+    loss; at the end one fp64 fold on the device (``ops.regression_metrics``, chunks of ``batch_size`` rows = the
+    loader's batches) and ONE ``.cpu()``."""
+    from .. import ops
+    model.eval()
+    device = next(model.regressor.parameters()).device
+    packed = _packed_head(model)
+    if packed is None:
+        return validate_one_epoch(model, dataloader, build_loss_fn(loss_name), device, target_names, normalizer)
+    build_loss_fn(loss_name)                   # the same names are accepted, the same error for any other
+    mean, std = _normalizer_vectors(normalizer, device)
+    preds, tgts, losses = [], [], []
+    with torch.no_grad():
+        for images, targets in dataloader:
+            images = images.to(device, non_blocking=True)
+            targets = targets.to(device=device, dtype=torch.float32, non_blocking=True).contiguous()
+            if targets.shape[0] > batch_size or (preds and preds[-1].shape[0] != batch_size):
+                raise ValueError("evaluate_on_device: the loader's batches must be batch_size rows, the last one at most")
+            flat = torch.flatten(model.vae.encode_deterministic(images), start_dim=1)
+            pred, rowloss = ops.mlp_head_fwd(flat, *packed, mean=mean, std=std, targets=targets, loss=loss_name.lower())
+            preds.append(pred)
+            tgts.append(targets)
+            losses.append(rowloss)
+    if not preds:
+        raise RuntimeError("Validation dataloader produced zero batches.")
+    t = len(target_names)
+    folded = ops.regression_metrics(torch.cat(preds), torch.cat(tgts), torch.cat(losses), batch_size).cpu().tolist()
+    metrics: dict[str, float] = {"mae": folded[2 * t + 1], "mse": folded[2 * t + 2]}
+    for i, name in enumerate(target_names):
+        metrics[f"mae_{name}"], metrics[f"mse_{name}"] = folded[1 + i], folded[1 + t + i]
+    return folded[0], metrics
