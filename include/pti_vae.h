@@ -544,6 +544,34 @@ int pti_mlp_head_fwd(const float* x, int64_t ldx, int n, int d, const float* par
 int pti_regression_metrics(const float* pred, const float* targets, const float* rowloss, int n, int t, int batch,
                            double* out, pti_stream_t s);
 
+/* ---- train-time geometric augmentation (the pipeline of the reference's src/pti_ldm_vae/data/augmentation.py as one
+ *      displacement field and one gather; csrc/augment.hip) ----
+ * pti_elastic_field: field[b][c] = alpha[b] * (G_sigma * n[b][c]), fp32 [B][2][H][W], channel 0 the x and channel 1 the y
+ *   displacement in pixels.  One launch, no workspace, no atomics.
+ *   n[b][c][y][x] is uniform in [-1, 1) and a pure function of (keys[b], c, i = y * W + x) in 32-bit arithmetic:
+ *       mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16        (lowbias32)
+ *       h = mix(mix(i + lo32(key)) ^ hi32(key) ^ (c * 0x9e3779b9));   n = ((h >> 8) - 2^23) / 2^23   (exact in fp32)
+ *   G_sigma is scipy.ndimage.gaussian_filter(mode="reflect", truncate=4.0): radius int(4 sigma + 0.5), taps
+ *   exp(-k^2 / 2 sigma^2) normalised (computed in fp64 on the host, cast once), applied along x then along y, borders by
+ *   symmetric reflection d c b a | a b c d | d c b a.  Every output is one fmaf chain over the taps in ascending order
+ *   per pass: a sample's field depends on its key, H, W and sigma only -- bitwise the same alone or in any batch.
+ *   keys: uint64 [B] and alpha: fp32 [B] are DEVICE arrays; a sample with alpha == 0 gets zeros without the blur work.
+ *   PTI_EINVAL before any launch: null pointers, dimensions < 1, sigma <= 0, radius > min(H, W) (one reflection must
+ *   reach); PTI_EUNSUPPORTED: radius > PTI_ELASTIC_MAX_RADIUS (the LDS tile), B > 32767, H * W > 2^30.
+ * pti_augment_warp: out[b][c][y][x] = bilinear sample of src[b][c] at s = M_b * (x + fx, y + fy, 1), pixel centres on
+ *   integers, M_b = mat[b][0..5] the row-major 2x3 INVERSE map (output pixel -> source position), (fx, fy) =
+ *   field[b][0..1][y][x] or 0 when field is NULL.  Taps outside the image contribute zero
+ *   (scipy.ndimage.map_coordinates(order=1, mode="grid-constant", cval=0)).  One launch for the batch; the coordinate
+ *   and the tap weights are computed once per pixel for all channels.  s is two fmaf chains, so a lattice map (entries
+ *   0 / +-1, integer offsets, no field) gives exact integer coordinates, weights of exactly 0 and 1 and the source
+ *   values unchanged.  src / out fp32 [B][C][H][W]; out must not overlap src (PTI_EINVAL, as null pointers and
+ *   dimensions < 1); B > 65535: PTI_EUNSUPPORTED.                                                                       */
+#define PTI_ELASTIC_MAX_RADIUS 30
+int pti_elastic_field(const uint64_t* keys, const float* alpha, float sigma, int b, int h, int w, float* field,
+                      pti_stream_t s);
+int pti_augment_warp(const float* src, const float* mat, const float* field, int b, int c, int h, int w, float* out,
+                     pti_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,8 @@ SIGNATURES = {
     "pti_mlp_head_ws_floats": (_I64, [_I, _I, C.POINTER(C.c_int32), _I]),
     "pti_mlp_head_fwd": (_I, [_P, _I64, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "pti_regression_metrics": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "pti_elastic_field": (_I, [_P, _P, _F, _I, _I, _I, _P, _P]),
+    "pti_augment_warp": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

@@ -10,3 +10,8 @@ __all__ = ["DeviceImageLoader", "create_regression_dataloaders", "create_vae_dat
 from .loader import create_regression_eval_dataloader, create_regression_inference_dataloader  # noqa: E402
 
 __all__ += ["create_regression_eval_dataloader", "create_regression_inference_dataloader"]
+
+# train-time augmentation
+from .augment import AugmentPolicy, draw_params  # noqa: E402
+
+__all__ += ["AugmentPolicy", "draw_params"]

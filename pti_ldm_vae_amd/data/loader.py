@@ -92,9 +92,13 @@ class DeviceImageLoader:
 
     def __init__(self, paths: list[str], batch_size: int, patch_size: tuple[int, int], device, *, rank: int = 0,
                  world_size: int = 1, shuffle: bool = True, seed: int = 42, num_workers: int = 4,
-                 attributes: list[dict[str, float]] | None = None, target_names: list[str] | None = None):
+                 attributes: list[dict[str, float]] | None = None, target_names: list[str] | None = None,
+                 augment: "AugmentPolicy | None" = None):
         """``attributes``: one {name: value} dict per path; batches become ``(images, {name: [b] tensor})``.  With
-        ``target_names`` the values are instead stacked in that order: ``(images, [b, T] tensor)`` (regression)."""
+        ``target_names`` the values are instead stacked in that order: ``(images, [b, T] tensor)`` (regression).
+        ``augment``: a ``data.augment.AugmentPolicy``; every image is then warped on the copy stream, after
+        preprocessing, by the transform its ``(seed, epoch, dataset index)`` draws.  ``None``: no
+        augmentation code runs at all."""
         from .. import ops
         self._ops = ops
         self.paths, self.batch, self.patch = list(paths), int(batch_size), (int(patch_size[0]), int(patch_size[1]))
@@ -106,6 +110,7 @@ class DeviceImageLoader:
         self.pool = ThreadPoolExecutor(max_workers=max(1, num_workers))
         self.copy_stream = torch.cuda.Stream(device=self.dev)
         self._slots = [dict(pinned=None, dev=None, out=None, stats=None, event=None) for _ in range(3)]
+        self.augment = augment
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
@@ -142,7 +147,10 @@ class DeviceImageLoader:
             slot["dev"][:total].copy_(slot["pinned"][:total], non_blocking=True)
             d_off = desc.to(self.dev, non_blocking=True)
             d_hw = hw.to(self.dev, non_blocking=True)
-            self._ops.preprocess_batch(slot["dev"], d_off, d_hw, out)
+            if self.augment is None:
+                self._ops.preprocess_batch(slot["dev"], d_off, d_hw, out)
+            else:
+                self._augment(slot, idx, d_off, d_hw, out)
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         slot["event"], slot["out"], slot["keep"] = ev, out, (desc, hw, d_off, d_hw)
@@ -156,6 +164,41 @@ class DeviceImageLoader:
             slot["keep"] += (host,)
             slot["attrs"] = (names, dev_attrs)
         return slot
+
+    def _augment(self, slot: dict, idx: list[int], d_off, d_hw, out) -> None:
+        """On the copy stream: preprocess into the slot's scratch, then warp into ``out`` (the tensor that is yielded).
+        The parameter table -- per sample the 2x3 inverse map, the elastic amplitude and the 64-bit key -- is drawn on
+        the host for the batch's DATASET indices, written into the slot's pinned buffer and uploaded in one copy.  The
+        warp's zero fill is the background value of the normalised image, so "exact zero = background" holds outside the
+        warped foreground and no second statistics pass is needed."""
+        from .augment import draw_params
+        b, (hp, wp), cap = len(idx), self.patch, self.batch
+        if slot.get("aug") is None:
+            # int64 words: [cap * 7 floats (mat, then alpha) padded to whole words | cap keys]
+            words = (7 * cap + 1) // 2 + cap
+            slot["aug"] = dict(host=torch.empty(words, dtype=torch.int64).pin_memory(),
+                               dev=torch.empty(words, dtype=torch.int64, device=self.dev),
+                               pre=torch.empty(cap, 1, hp, wp, dtype=torch.float32, device=self.dev), field=None)
+        aug = slot["aug"]
+        if slot["event"] is not None:
+            slot["event"].synchronize()   # the upload that last read this pinned table (a new epoch restarts at slot 0)
+        fwords = (7 * cap + 1) // 2
+        h_f32, h_key = aug["host"][:fwords].view(torch.float32).numpy(), aug["host"][fwords:].numpy().view(np.uint64)
+        for j, i in enumerate(idx):
+            mat, key, alpha = draw_params(self.augment, self.seed, self.epoch, i, hp, wp)
+            h_f32[6 * j:6 * j + 6], h_f32[6 * cap + j], h_key[j] = mat, alpha, key
+        elastic = bool((h_f32[6 * cap:6 * cap + b] != 0).any())
+        aug["dev"].copy_(aug["host"], non_blocking=True)
+        d_f32, d_key = aug["dev"][:fwords].view(torch.float32), aug["dev"][fwords:]
+        pre = aug["pre"][:b]
+        self._ops.preprocess_batch(slot["dev"], d_off, d_hw, pre)
+        field = None
+        if elastic:
+            if aug["field"] is None:
+                aug["field"] = torch.empty(cap, 2, hp, wp, dtype=torch.float32, device=self.dev)
+            field = self._ops.elastic_field(d_key[:b], d_f32[6 * cap:6 * cap + b], self.augment.elastic_sigma, hp, wp,
+                                            out=aug["field"][:b])
+        self._ops.augment_warp(pre, d_f32[:6 * b].view(b, 6), field, out=out)
 
     def __iter__(self):
         idx = shard_indices(len(self.paths), self.rank, self.world, self.shuffle, self.seed, self.epoch)
@@ -195,10 +238,13 @@ def create_vae_dataloaders(data_base_dir: str, batch_size: int, patch_size: tupl
                            seed: int | None = 42, subset_size: int | None = None, val_dir: str | None = None,
                            cache_rate: float = 0.0, distributed: bool = False, world_size: int = 1,
                            ar_vae_enabled: bool = False, regularized_attributes: dict | None = None, device="cuda",
-                           **_ignored):
+                           augment=False, **_ignored):
     """Same signature and return shape as the reference's ``create_vae_dataloaders`` (dataloaders.py:370-593):
     ``(train_loader, val_loader, train_paths, val_paths)`` with loaders that yield device batches -- ``images``, or
-    ``(images, attributes)`` when ``ar_vae_enabled``."""
+    ``(images, attributes)`` when ``ar_vae_enabled``.  ``augment`` (the config key: ``False`` / ``True`` / a dict of
+    ``AugmentPolicy`` fields, or a policy) applies to the TRAIN loader only; ``train.augment`` is the policy in effect."""
+    from .augment import AugmentPolicy
+    policy = AugmentPolicy.from_config(augment, ar_vae_enabled)
     if not 0 < train_split < 1:
         raise ValueError(f"train_split must be in (0, 1), got {train_split}")
     paths = list_tif_paths(data_base_dir, data_source)
@@ -215,7 +261,7 @@ def create_vae_dataloaders(data_base_dir: str, batch_size: int, patch_size: tupl
     r = rank if distributed else 0
     s = seed if seed is not None else 0
     train = DeviceImageLoader(train_paths, batch_size, patch_size, device, rank=r, world_size=world, shuffle=True, seed=s,
-                              num_workers=num_workers, attributes=train_attrs)
+                              num_workers=num_workers, attributes=train_attrs, augment=policy)
     val = DeviceImageLoader(val_paths, batch_size, patch_size, device, rank=r, world_size=world, shuffle=False, seed=s,
                             num_workers=num_workers, attributes=val_attrs)
     return train, val, train_paths, val_paths

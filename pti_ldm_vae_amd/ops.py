@@ -1478,3 +1478,60 @@ def regression_metrics(pred, targets, rowloss, batch):
     L.check(L.lib().pti_regression_metrics(_ptr(pred), _ptr(targets), _ptr(rowloss), n, t, int(batch), _ptr(out), _stream()),
             "pti_regression_metrics")
     return out
+
+
+# ---- train-time augmentation (csrc/augment.hip; include/pti_vae.h "train-time geometric augmentation") -----------------
+ELASTIC_MAX_RADIUS = 30   # PTI_ELASTIC_MAX_RADIUS
+
+
+def elastic_field(keys, alpha, sigma, h, w, out=None):
+    """Smoothed random displacement field (``pti_elastic_field``): ``keys`` int64 / uint64 [B] (the 64 key bits of every
+    sample), ``alpha`` fp32 [B], both on the device -> fp32 ``[B, 2, h, w]``, channel 0 the x and 1 the y displacement in
+    pixels: ``alpha[b]`` times the hash noise of ``keys[b]`` under ``scipy.ndimage.gaussian_filter(sigma, mode="reflect")``.
+    A sample's field depends on its key alone; ``alpha == 0`` gives zeros.  Runs on the current stream, no host sync."""
+    if not isinstance(keys, torch.Tensor) or keys.dtype not in (I64, torch.uint64):
+        raise TypeError(f"elastic_field: keys must be an int64 or uint64 tensor, got {getattr(keys, 'dtype', type(keys))}")
+    _chk(keys, keys.dtype, "elastic_field: keys", 1)
+    _chk(alpha, F32, "elastic_field: alpha", 1)
+    b, h, w, sigma = keys.numel(), int(h), int(w), float(sigma)
+    if b < 1 or alpha.numel() != b or alpha.device != keys.device:
+        raise ValueError("elastic_field: keys and alpha must be [B] with B >= 1 on one device")
+    if h < 1 or w < 1 or not sigma > 0.0:
+        raise ValueError(f"elastic_field: need h, w >= 1 and sigma > 0, got {h}, {w}, {sigma}")
+    radius = int(4.0 * sigma + 0.5)
+    if radius > min(h, w) or radius > ELASTIC_MAX_RADIUS:
+        raise ValueError(f"elastic_field: radius {radius} of sigma {sigma} must not exceed min(h, w) = {min(h, w)} "
+                         f"nor {ELASTIC_MAX_RADIUS}")
+    if out is None:
+        out = torch.empty(b, 2, h, w, dtype=F32, device=keys.device)
+    else:
+        _chk(out, F32, "elastic_field: out", 4)
+        if tuple(out.shape) != (b, 2, h, w) or out.device != keys.device:
+            raise ValueError(f"elastic_field: out must be [{b}, 2, {h}, {w}] on {keys.device}")
+    L.check(L.lib().pti_elastic_field(_ptr(keys), _ptr(alpha), sigma, b, h, w, _ptr(out), _stream()), "pti_elastic_field")
+    return out
+
+
+def augment_warp(src, mat, field=None, out=None):
+    """One bilinear gather for a batch (``pti_augment_warp``): ``out[b, c, y, x]`` = ``src[b, c]`` sampled at
+    ``mat[b] @ (x + field[b, 0, y, x], y + field[b, 1, y, x], 1)``, taps outside the image contributing zero.
+    ``src`` fp32 [B, C, H, W]; ``mat`` fp32 [B, 6] (row-major 2x3 inverse map, pixel centres on integers); ``field`` fp32
+    [B, 2, H, W] or None; ``out`` must not share memory with ``src``.  Runs on the current stream, no host sync."""
+    _chk(src, F32, "augment_warp: src", 4)
+    _chk(mat, F32, "augment_warp: mat", 2)
+    b, c, h, w = src.shape
+    if min(b, c, h, w) < 1 or tuple(mat.shape) != (b, 6) or mat.device != src.device:
+        raise ValueError(f"augment_warp: src must be a non-empty [B, C, H, W] and mat [B, 6] on its device, got "
+                         f"{tuple(src.shape)}, {tuple(mat.shape)}")
+    if field is not None:
+        _chk(field, F32, "augment_warp: field", 4)
+        if tuple(field.shape) != (b, 2, h, w) or field.device != src.device:
+            raise ValueError(f"augment_warp: field must be [{b}, 2, {h}, {w}] on {src.device}")
+    if out is None:
+        out = torch.empty_like(src)
+    else:
+        _chk(out, F32, "augment_warp: out", 4)
+        if out.shape != src.shape or out.device != src.device:
+            raise ValueError("augment_warp: out must have the shape and device of src")
+    L.check(L.lib().pti_augment_warp(_ptr(src), _ptr(mat), _ptr(field), b, c, h, w, _ptr(out), _stream()), "pti_augment_warp")
+    return out

@@ -23,7 +23,8 @@ What is different, on purpose:
   * the AR-VAE term (``regularized_attributes``) IS part of the native step (``pti_ar_vae_loss``);
   * data: without ``--synthetic`` the TIFF directory of the config is read through the device input pipeline
     (``pti_ldm_vae_amd.data``: host decode -> one H2D copy -> GPU resize + masked z-score; attribute JSONs joined
-    for AR-VAE); ``--synthetic N`` trains on N seeded synthetic images of the configured patch size (z-scored
+    for AR-VAE; with the config's ``augment`` the train batches are warped there too, ``data/augment.py``, and the policy
+    in effect is the first record of ``metrics.jsonl``); ``--synthetic N`` trains on N seeded synthetic images of the configured patch size (z-scored
     elliptical foreground, zero background; U(0,1) attributes), sharded across ranks like ``DistributedSampler``;
   * logging goes to ``<run_dir>/metrics.jsonl`` with the reference's W&B metric names
     (``train/recon_loss`` ... ``val/loss_total``), one host sync per ``--log-every`` steps.
@@ -143,12 +144,13 @@ class TiffShards:
     """The same ``batches(epoch, train)`` interface over a directory of .tif images (pti_ldm_vae_amd.data)."""
 
     def __init__(self, base_dir, batch, patch, rank, world, seed, device, *, data_source, train_split, subset_size, val_dir,
-                 num_workers, ar_vae_enabled=False, regularized_attributes=None):
+                 num_workers, ar_vae_enabled=False, regularized_attributes=None, augment=False):
         from .data import create_vae_dataloaders
         self.train, self.val, self.train_paths, self.val_paths = create_vae_dataloaders(
             base_dir, batch, patch, rank=rank, data_source=data_source, train_split=train_split, num_workers=num_workers,
             seed=seed, subset_size=subset_size, val_dir=val_dir, distributed=world > 1, world_size=world, device=device,
-            ar_vae_enabled=ar_vae_enabled, regularized_attributes=regularized_attributes)
+            ar_vae_enabled=ar_vae_enabled, regularized_attributes=regularized_attributes, augment=augment)
+        self.augment = self.train.augment     # the policy in effect (None: off)
 
     def batches(self, epoch, train=True):
         loader = self.train if train else self.val
@@ -264,6 +266,9 @@ def main(argv=None):
                                args.seed, device, args.train_split, attr_names=ar.names if ar else None)
         train_files = [f"synthetic:{i}" for i in range(data.n_train)]
         val_files = [f"synthetic:{i}" for i in range(data.n_train, data.n_train + data.n_val)]
+        policy = None
+        if getattr(args, "augment", False) and rank == 0:
+            print("[INFO] --synthetic: the config's `augment` is ignored (synthetic batches are not augmented)")
     else:
         # TIFF directory -> device batches (create_vae_dataloaders, train_vae.py:832-850 of the reference)
         if args.autoencoder_def["in_channels"] != 1:
@@ -271,13 +276,17 @@ def main(argv=None):
         data = TiffShards(args.data_base_dir, tr["batch_size"], tuple(tr["patch_size"]), rank, world, args.seed, device,
                           data_source=getattr(args, "data_source", "edente"), train_split=args.train_split,
                           subset_size=args.subset_size, val_dir=getattr(args, "val_dir", None), num_workers=args.num_workers,
-                          ar_vae_enabled=ar_enabled, regularized_attributes=reg_attrs)
+                          ar_vae_enabled=ar_enabled, regularized_attributes=reg_attrs, augment=getattr(args, "augment", False))
         train_files, val_files = data.train_paths, data.val_paths
+        policy = data.augment
     if rank == 0:
         with open(Path(args.run_dir) / "splits" / "vae_split.json", "w", encoding="utf-8") as f:
             json.dump({"seed": args.seed, "train_split": args.train_split, "subset_size": args.subset_size,
                        "val_dir": args.val_dir, "train_files": train_files, "val_files": val_files}, f, indent=2)
     log = open(Path(args.run_dir) / "metrics.jsonl", "a") if rank == 0 else None
+    if log is not None:     # first record of the run: the augmentation policy in effect (null: none)
+        log.write(json.dumps({"augment": policy.to_dict() if policy is not None else None}) + "\n")
+        log.flush()
     kl_w, max_epochs, val_interval = tr["kl_weight"], tr["max_epochs"], tr["val_interval"]
     for epoch in range(start_epoch, max_epochs):
         t0 = time.time()

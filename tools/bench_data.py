@@ -25,18 +25,20 @@ def main():
             write_tiff(os.path.join(d, f"{i:05d}.tif"), (rng.standard_normal((src, src)).astype(np.float32) * 300 + 900) * mask)
         paths = list_tif_paths(d)
         dev = torch.device("cuda:0")
-        ld = DeviceImageLoader(paths, batch, (patch, patch), dev, shuffle=True, seed=1, num_workers=workers)
-        for epoch in range(2):          # epoch 0 warms the page cache and the allocator
-            ld.set_epoch(epoch)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            seen = 0
-            for b in ld:
-                seen += b.shape[0]
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-        print(f"device pipeline: {seen / dt:9.1f} img/s  ({n} x {src}x{src} f32 TIFF -> {patch}x{patch}, batch {batch}, "
-              f"{workers} decode threads, {src * src * 4 * seen / dt / 1e9:.2f} GB/s of pixels)")
+        from pti_ldm_vae_amd.data import AugmentPolicy
+        for tag, policy in (("device pipeline", None), ("device pipeline + augment", AugmentPolicy())):
+            ld = DeviceImageLoader(paths, batch, (patch, patch), dev, shuffle=True, seed=1, num_workers=workers, augment=policy)
+            for epoch in range(3):          # epoch 0 warms the page cache and the allocator; the last one counts
+                ld.set_epoch(epoch)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                seen = 0
+                for b in ld:
+                    seen += b.shape[0]
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+            print(f"{tag}: {seen / dt:9.1f} img/s  ({n} x {src}x{src} f32 TIFF -> {patch}x{patch}, batch {batch}, "
+                  f"{workers} decode threads, {src * src * 4 * seen / dt / 1e9:.2f} GB/s of pixels)")
         t0 = time.perf_counter()
         k = min(n, 64)
         for p in paths[:k]:
