@@ -35,7 +35,8 @@ typedef void* pti_stream_t; /* hipStream_t */
                                or constant changed), so a caller built against the earlier 5 keeps working.  The same holds
                                for pti_mask_geometry, appended after those.
                                Still 5: pti_mlp_head_fwd / pti_mlp_head_ws_floats / pti_regression_metrics, appended after
-                               pti_mask_geometry in the same way. */
+                               pti_mask_geometry in the same way.
+                               Still 5: pti_conv_wgrad_batched_mode (a host-only query) appended in the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -208,6 +209,10 @@ typedef struct pti_wgrad_job {
 } pti_wgrad_job;
 int pti_conv_wgrad_mfma_batched(const pti_wgrad_job* jobs, int njobs, void* workspace, int64_t workspace_bytes,
                                 pti_stream_t s);
+/* The kernel mode 0..3 that pti_conv_wgrad_mfma_batched files a job of this shape under (one partial launch per mode
+ * present in a call, issued 3, 2, 1, 0), or a negative value for a shape it refuses.  Pure host arithmetic (reads the
+ * PTI_WGRAD_V6 / PTI_WGRAD_V4_COB2 knobs the way the launch does); no GPU call.  */
+int pti_conv_wgrad_batched_mode(int n, int h, int w, int cin, int cout);
 
 /* ---- GroupNorm(+SiLU) backward, 2x2 sum pool ---------------------------------------------- */
 /* dx = d/dx of act(GroupNorm(x)) given da (+ dres added), dgamma/dbeta += ; sums: float [n][c][2] scratch

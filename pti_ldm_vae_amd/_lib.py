@@ -96,6 +96,7 @@ SIGNATURES = {
     "pti_conv_wgrad_mfma": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, C.POINTER(ConvDesc), _P]),
     "pti_conv_wgrad_mfma_partials": (_I, [_P, _P, _P, _P, _P, _P, _I64, C.POINTER(ConvDesc), C.POINTER(_I), _P]),
     "pti_conv_wgrad_mfma_batched": (_I, [C.POINTER(WgradJob), _I, _P, _I64, _P]),
+    "pti_conv_wgrad_batched_mode": (_I, [_I, _I, _I, _I, _I]),
     "pti_direct_repack": (_I, [C.POINTER(DirectRepackTable), _P]),
     "pti_conv_wgrad_reduce": (_I, [_P, _I, _P, _P, _I, C.POINTER(ConvDesc), _P]),
     "pti_gn_bwd_blocks": (_I, [_I, _I, _I]),

@@ -1569,18 +1569,28 @@ static int w6_mode(int n, int h, int w, int cin, int cout) {
   if (v >= 2 && cout % 64 == 0 && cin % 64 == 0 && (v == 2 || (long long)h * w <= 128 * 128)) return 3;
   return 0;
 }
-static void w4_fill_job(W4Job& a, const void* x, const void* dy, int n, int h, int w, int cin, int cout, int v6 = 0) {
+static void w4_fill_job(W4Job& a, const void* x, const void* dy, int n, int h, int w, int cin, int cout, int mode) {
   a.x = (const bf16*)x; a.dy = (const bf16*)dy; a.slab = nullptr;
   a.N = n; a.H = h; a.W = w; a.Cin = cin; a.Cout = cout;
-  a.tiles_x = cdiv(w, TW); a.tiles_y = cdiv(h, v6 == 2 ? W6A::TH_ : TH); a.ntiles = n * a.tiles_x * a.tiles_y;
+  a.tiles_x = cdiv(w, TW); a.tiles_y = cdiv(h, mode == 2 ? W6A::TH_ : TH); a.ntiles = n * a.tiles_x * a.tiles_y;
   a.slab_stride = (long long)9 * cout * cin + cout;
   a.S = 1;
-  static const int cob2_env = getenv("PTI_WGRAD_V4_COB2") ? atoi(getenv("PTI_WGRAD_V4_COB2")) : 1;
-  a.cob2 = v6 ? v6 : ((cob2_env && cout % 64 == 0) ? 1 : 0);
+  a.cob2 = mode;
 }
 static bool w4_eligible(int n, int h, int w, int cin, int cout) {
   return n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && cin % 32 == 0 && cout % 32 == 0 &&
          (long long)n * h * w * cin * 2 < (1ll << 31) && (long long)n * h * w * cout * 2 < (1ll << 31);
+}
+// Mode of a job that the v6 rule leaves to the v4 kernel (pti_conv_wgrad_reduce fills its job with this one only).
+static int w4_mode(int cout) {
+  static const int cob2_env = getenv("PTI_WGRAD_V4_COB2") ? atoi(getenv("PTI_WGRAD_V4_COB2")) : 1;
+  return (cob2_env && cout % 64 == 0) ? 1 : 0;
+}
+// The one place a job's kernel mode is decided; < 0: not a v4 / v6 job at all.  Host arithmetic only.
+extern "C" int pti_conv_wgrad_batched_mode(int n, int h, int w, int cin, int cout) {
+  if (!w4_eligible(n, h, w, cin, cout)) return PTI_EUNSUPPORTED;
+  const int v4 = w4_mode(cout), v6 = w6_mode(n, h, w, cin, cout);
+  return v6 ? v6 : v4;
 }
 // Tuning aid that yields GARBAGE results (see WgArgs::diag): honoured only together with the explicit second opt-in
 // PTI_ALLOW_WRONG_RESULTS=1, and announced on stderr; bench.py / train_vae.py refuse to run with either variable set.
@@ -1748,7 +1758,7 @@ extern "C" int pti_conv_wgrad_mfma_partials(const void* x, const void* dy, const
   if (v4) {
     W4Batch b;
     b.njobs = 1;
-    w4_fill_job(b.job[0], x, dy, d->n, d->h, d->w, d->cin, d->cout, w6_mode(d->n, d->h, d->w, d->cin, d->cout));
+    w4_fill_job(b.job[0], x, dy, d->n, d->h, d->w, d->cin, d->cout, pti_conv_wgrad_batched_mode(d->n, d->h, d->w, d->cin, d->cout));
     b.dw[0] = b.dbias[0] = nullptr;
     b.accumulate[0] = 0;
     if (w4_plan(b, (float*)workspace, workspace_bytes / 4) < 0)
@@ -1786,7 +1796,7 @@ extern "C" int pti_conv_wgrad_reduce(const void* workspace, int splits, float* d
     if (kk != 9 || !w4_eligible(d->n, d->h, d->w, d->cin, d->cout)) PTI_FAIL(PTI_EINVAL, "conv_wgrad_reduce: block-ordered slabs are 3x3 only");
     W4Batch b;
     b.njobs = 1;
-    w4_fill_job(b.job[0], nullptr, nullptr, d->n, d->h, d->w, d->cin, d->cout);
+    w4_fill_job(b.job[0], nullptr, nullptr, d->n, d->h, d->w, d->cin, d->cout, w4_mode(d->cout));
     b.job[0].S = splits & ~PTI_WGRAD_SLAB_V4;
     b.job[0].slab = (float*)workspace;
     b.dw[0] = dw; b.dbias[0] = dbias; b.accumulate[0] = accumulate;
@@ -1823,12 +1833,13 @@ extern "C" int pti_conv_wgrad_mfma_batched(const pti_wgrad_job* jobs, int njobs,
   for (int j = 0; j < njobs; ++j) {
     const pti_wgrad_job& q = jobs[j];
     if (!q.x || !q.dy || !q.dw) PTI_FAIL(PTI_EINVAL, "conv_wgrad_mfma_batched: job %d has a null pointer", j);
-    if (!w4_eligible(q.n, q.h, q.w, q.cin, q.cout))
+    const int mode = pti_conv_wgrad_batched_mode(q.n, q.h, q.w, q.cin, q.cout);
+    if (mode < 0)
       PTI_FAIL(PTI_EUNSUPPORTED, "conv_wgrad_mfma_batched: job %d: n=%d h=%d w=%d cin=%d cout=%d (channels must be multiples of 32, tensors < 2 GiB)",
                j, q.n, q.h, q.w, q.cin, q.cout);
     W4Job jb;
-    w4_fill_job(jb, q.x, q.dy, q.n, q.h, q.w, q.cin, q.cout, w6_mode(q.n, q.h, q.w, q.cin, q.cout));
-    W4Batch& b = bm[jb.cob2];
+    w4_fill_job(jb, q.x, q.dy, q.n, q.h, q.w, q.cin, q.cout, mode);
+    W4Batch& b = bm[mode];
     const int k = b.njobs++;
     b.job[k] = jb;
     b.dw[k] = q.dw; b.dbias[k] = q.dbias; b.accumulate[k] = q.accumulate;

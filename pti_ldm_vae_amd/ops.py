@@ -21,6 +21,9 @@ F32 = torch.float32
 I64 = torch.int64
 STAT_SCALE = 65536.0   # GroupNorm statistics are Q47.16 fixed-point int64 {sum, sum of squares} (pti_common.h)
 ACT16 = (BF16, F16)   # storage formats of a forward activation (flag derived from the tensor's dtype)
+LATENT_BWD_MAX_BLOCKS = 512   # PTI_LATENT_BWD_MAX_BLOCKS / PTI_VAE_LOSS_MAX_BLOCKS / PTI_POST_QUANT_BWD_MAX_BLOCKS of
+VAE_LOSS_MAX_BLOCKS = 1024    # include/pti_vae.h
+POST_QUANT_BWD_MAX_BLOCKS = 256
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -49,6 +52,31 @@ def _chk(t, dtype, name, dims=None):
         raise ValueError(f"{name}: must be contiguous")
     if dims is not None and t.dim() != dims:
         raise ValueError(f"{name}: expected {dims} dims, got {tuple(t.shape)}")
+
+
+def _out(out, shape, dtype, device, name, chk_name=None, rank=True, msg=None):
+    """The caller-supplied output ``out`` checked (contiguous ``dtype`` of ``shape`` on ``device``), or a new tensor when
+    there is none.  ``chk_name`` / ``rank`` / ``msg``: the site's own name in _chk's errors, whether _chk sees the rank, and
+    the text of the shape / device error, where a site's differ from the common ones."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _chk(out, dtype, chk_name or name, len(shape) if rank else None)
+    if tuple(out.shape) != tuple(shape) or out.device != device:
+        raise ValueError(msg or f"{name} must be {list(shape)} on {device}")
+    return out
+
+
+_SCRATCH = {}
+
+
+def _scratch(kind, shape, floats, device, stream):
+    """fp32 scratch of ``floats`` elements, cached per (kind, device, stream, shape): launches on one stream are ordered,
+    so they can share it; two streams never do."""
+    key = (kind, device.index, stream) + tuple(shape)
+    ws = _SCRATCH.get(key)
+    if ws is None:
+        ws = _SCRATCH[key] = torch.empty(floats, dtype=F32, device=device)
+    return ws
 
 
 def conv_out_hw(h, w, mode):
@@ -127,6 +155,53 @@ def _chk_stats(t, count, name):
         raise ValueError(f"{name}: expected {count} fixed-point sums, got {t.numel()}")
 
 
+def _chk_prologue(who, in_stats, gamma, beta, n, groups, cin):
+    _chk_stats(in_stats, n * groups * 2, "in_stats")
+    for t, nm in ((gamma, "gamma"), (beta, "beta")):
+        _chk(t, F32, nm)
+        if t.numel() != cin:
+            raise ValueError(f"{who}: {nm} size")
+
+
+# Set to a list to make the MFMA conv / weight-gradient launchers record (kernel name, algorithmic flops, bytes, start
+# event, end event, shape) per launch on the current stream -- used by bench.py for the roofline line and its per-shape
+# table; None costs nothing.  The kernel name is the symbol the HIP runtime reports for the launch
+# (pti_last_kernel_name), shortened the way tools/pmc_traffic.py shortens rocprofv3's Kernel_Name column.
+KERNEL_PROFILE = None
+_MODE_NAME = {PTI_CONV_S1: "s1", PTI_CONV_S2PAD: "s2", PTI_CONV_UP2: "up2", PTI_CONV_ZINS: "zins"}
+
+
+def last_kernel_name() -> str:
+    name = (L.lib().pti_last_kernel_name() or b"").decode()
+    name = name.replace("(anonymous namespace)::", "")
+    if name.startswith("void "):
+        name = name[5:]
+    depth = 0
+    for i, ch in enumerate(name):       # drop the trailing argument list, keep template arguments
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif ch == "(" and depth == 0:
+            return name[:i].strip()
+    return name.strip()
+
+
+def _prof_begin(prof):
+    """Open a KERNEL_PROFILE record: the start event goes onto the current stream right before the launch to be timed.
+    The launchers call this only when profiling is on (``prof`` is the list)."""
+    e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    e0.record()
+    return prof, e0, e1
+
+
+def _prof_end(rec, flops, nbytes, shape):
+    """Close it right after that launch, before any further pti_* call replaces the kernel name."""
+    prof, e0, e1 = rec
+    e1.record()
+    prof.append((last_kernel_name(), flops, nbytes, e0, e1, shape))
+
+
 def stats_to_float(stats):
     """Fixed-point {sum, sumsq} -> float64 tensor of the same shape (tests, diagnostics)."""
     return stats.double() / STAT_SCALE
@@ -170,11 +245,7 @@ def conv_mfma(x, w_packed, bias, y, *, cout, ksize=3, mode=PTI_CONV_S1, prologue
         if bias.numel() != cout:
             raise ValueError("conv_mfma: bias size")
     if prologue != PTI_PRO_NONE:
-        _chk_stats(in_stats, n * groups * 2, "in_stats")
-        for t, nm, cnt in ((gamma, "gamma", cin), (beta, "beta", cin)):
-            _chk(t, F32, nm)
-            if t.numel() != cnt:
-                raise ValueError(f"conv_mfma: {nm} size")
+        _chk_prologue("conv_mfma", in_stats, gamma, beta, n, groups, cin)
     if residual is not None:
         _chk(residual, ACT16, "residual", 4)
         if residual.shape != y.shape or pool2:
@@ -187,9 +258,7 @@ def conv_mfma(x, w_packed, bias, y, *, cout, ksize=3, mode=PTI_CONV_S1, prologue
                  res_f16=int(residual is not None and residual.dtype == F16), out_f16=int(y.dtype == F16),
                  pool2x2_out=int(pool2), w_f16=int(w_f16), relu_out=int(relu))
     prof = KERNEL_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    rec = None if prof is None else _prof_begin(prof)
     if act_out is not None:
         L.check(L.lib().pti_conv2d_mfma_saveact(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(in_stats), _ptr(gamma),
                                                 _ptr(beta), _ptr(residual), _ptr(y), _ptr(out_stats), _ptr(act_out),
@@ -198,40 +267,14 @@ def conv_mfma(x, w_packed, bias, y, *, cout, ksize=3, mode=PTI_CONV_S1, prologue
         L.check(L.lib().pti_conv2d_mfma(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(in_stats), _ptr(gamma), _ptr(beta),
                                         _ptr(residual), _ptr(y), _ptr(out_stats), C.byref(d), _stream()),
                 "pti_conv2d_mfma")
-    if prof is not None:
-        e1.record()
+    if rec is not None:
         # algorithmic work; the zero-insert data gradient only has 1/4 useful taps per output pixel
         flops = 2.0 * n * ho * wo * cout * cin * ksize * ksize * (0.25 if mode == PTI_CONV_ZINS else 1.0)
         # algorithmic bytes: read the input once (16-bit), write the output once (+ residual read, + side output)
         nbytes = 2.0 * (x.numel() * (2 if act_out is not None else 1) + y.numel() * (2 if residual is not None else 1))   # (pooled y counted as stored)
         kind = "conv fwd" if x.dtype == F16 or prologue != PTI_PRO_NONE else "conv dgrad"
-        prof.append((last_kernel_name(), flops, nbytes, e0, e1,
-                     (kind, cin, cout, ho, wo, ksize, {PTI_CONV_S1: "s1", PTI_CONV_S2PAD: "s2", PTI_CONV_UP2: "up2",
-                                                       PTI_CONV_ZINS: "zins"}[mode], n)))
+        _prof_end(rec, flops, nbytes, (kind, cin, cout, ho, wo, ksize, _MODE_NAME[mode], n))
     return y
-
-
-# Set to a list to make the MFMA conv / weight-gradient launchers record (kernel name, algorithmic flops, bytes, start
-# event, end event, shape) per launch on the current stream -- used by bench.py for the roofline line and its per-shape
-# table; None costs nothing.  The kernel name is the symbol the HIP runtime reports for the launch
-# (pti_last_kernel_name), shortened the way tools/pmc_traffic.py shortens rocprofv3's Kernel_Name column.
-KERNEL_PROFILE = None
-
-
-def last_kernel_name() -> str:
-    name = (L.lib().pti_last_kernel_name() or b"").decode()
-    name = name.replace("(anonymous namespace)::", "")
-    if name.startswith("void "):
-        name = name[5:]
-    depth = 0
-    for i, ch in enumerate(name):       # drop the trailing argument list, keep template arguments
-        if ch == "<":
-            depth += 1
-        elif ch == ">":
-            depth -= 1
-        elif ch == "(" and depth == 0:
-            return name[:i].strip()
-    return name.strip()
 
 
 def _strides4(t, layout):
@@ -318,11 +361,7 @@ def conv_wgrad_mfma(x, dy, dw, dbias, *, ksize=3, mode=PTI_CONV_S1, prologue=PTI
         if dbias.numel() != cout:
             raise ValueError("conv_wgrad_mfma: dbias size")
     if prologue != PTI_PRO_NONE:
-        _chk_stats(in_stats, n * groups * 2, "in_stats")
-        for t, nm, cnt in ((gamma, "gamma", cin), (beta, "beta", cin)):
-            _chk(t, F32, nm)
-            if t.numel() != cnt:
-                raise ValueError(f"conv_wgrad_mfma: {nm} size")
+        _chk_prologue("conv_wgrad_mfma", in_stats, gamma, beta, n, groups, cin)
     ws = workspace if workspace is not None else wgrad_workspace(x.device)
     d = ConvDesc(n=n, h=h, w=w, cin=cin, ho=ho, wo=wo, cout=cout, ksize=ksize, mode=mode, prologue=prologue,
                  groups=groups, eps=eps, in_f16=int(x.dtype == F16))
@@ -333,20 +372,16 @@ def conv_wgrad_mfma(x, dy, dw, dbias, *, ksize=3, mode=PTI_CONV_S1, prologue=PTI
                                             _stream()), "pti_conv_wgrad_mfma")
         return dw
     # profiling: the same two launches through the two-call form, with events around the partial (MFMA) kernel only
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     splits = C.c_int(0)
-    e0.record()
+    rec = _prof_begin(prof)
     L.check(L.lib().pti_conv_wgrad_mfma_partials(_ptr(x), _ptr(dy), _ptr(in_stats), _ptr(gamma), _ptr(beta), _ptr(ws),
                                                  ws.numel() * 4, C.byref(d), C.byref(splits), _stream()),
             "pti_conv_wgrad_mfma_partials")
-    e1.record()
-    name = last_kernel_name()
+    # algorithmic bytes: x and dy read once (16-bit); dw itself is negligible (the split-K slabs are not algorithmic)
+    _prof_end(rec, 2.0 * n * ho * wo * cout * cin * ksize * ksize, 2.0 * (x.numel() + dy.numel()),
+              ("conv wgrad", cin, cout, ho, wo, ksize, _MODE_NAME[mode], n))
     L.check(L.lib().pti_conv_wgrad_reduce(_ptr(ws), splits.value, _ptr(dw), _ptr(dbias), int(accumulate), C.byref(d),
                                           _stream()), "pti_conv_wgrad_reduce")
-    flops = 2.0 * n * ho * wo * cout * cin * ksize * ksize
-    # algorithmic bytes: x and dy read once (16-bit); dw itself is negligible (the split-K slabs are not algorithmic)
-    prof.append((name, flops, 2.0 * (x.numel() + dy.numel()), e0, e1,
-                 ("conv wgrad", cin, cout, ho, wo, ksize, {PTI_CONV_S1: "s1", PTI_CONV_S2PAD: "s2", PTI_CONV_UP2: "up2"}[mode], n)))
     return dw
 
 
@@ -362,7 +397,6 @@ def conv_wgrad_mfma_batched(jobs, workspace=None, accumulate=True):
     if not 1 <= len(jobs) <= L.WGRAD_BATCH_MAX:
         raise ValueError(f"conv_wgrad_mfma_batched: 1..{L.WGRAD_BATCH_MAX} jobs, got {len(jobs)}")
     arr = (L.WgradJob * len(jobs))()
-    flops = nbytes = 0.0
     for i, (x, dy, dw, db) in enumerate(jobs):
         _chk(x, BF16, "x", 4)
         _chk(dy, BF16, "dy", 4)
@@ -375,45 +409,28 @@ def conv_wgrad_mfma_batched(jobs, workspace=None, accumulate=True):
             _chk(db, F32, "dbias")
         arr[i] = L.WgradJob(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), n, h, w, cin,
                             cout, int(accumulate))
-        flops += 2.0 * n * h * w * cout * cin * 9
-        nbytes += 2.0 * (x.numel() + dy.numel())
     ws = workspace if workspace is not None else wgrad_workspace(jobs[0][0].device)
     prof = KERNEL_PROFILE
     if prof is None:
         L.check(L.lib().pti_conv_wgrad_mfma_batched(arr, len(jobs), _ptr(ws), ws.numel() * 4, _stream()),
                 "pti_conv_wgrad_mfma_batched")
         return
-    # profiling: the library launches one kernel per mode (wgrad_mfma.hip, w4_fill_job: the v6 kernel's two shapes, two
-    # output-channel blocks per workgroup for Cout % 64 == 0, tile pairs otherwise); issue the groups as separate calls
-    # so that each kernel gets its own record (its own algorithmic work, its own duration = partial launch + the <1 %
-    # reduction launch) under its own name
-    cob2 = os.environ.get("PTI_WGRAD_V4_COB2", "1") != "0"
-    v6 = int(os.environ.get("PTI_WGRAD_V6", "3") or 0)
-
-    def mode_of(x, cout):
-        cin = x.shape[3]
-        if v6 >= 1 and cout % 128 == 0 and cin % 64 == 0:
-            return 2
-        if v6 >= 2 and cout % 64 == 0 and cin % 64 == 0 and (v6 == 2 or x.shape[1] * x.shape[2] <= 128 * 128):
-            return 3
-        return 1 if cob2 and cout % 64 == 0 else 0
+    # profiling: the library launches one kernel per mode (pti_conv_wgrad_batched_mode: the v6 kernel's two shapes, two
+    # output-channel blocks per workgroup for Cout % 64 == 0, tile pairs otherwise); issue the groups as separate calls,
+    # in the library's order, so that each kernel gets its own record (its own algorithmic work, its own duration =
+    # partial launch + the <1 % reduction launch) under its own name.  A job the library refuses (mode < 0) goes last.
     groups = {}
-    for i, (x, dy, dw, db) in enumerate(jobs):
-        groups.setdefault(mode_of(x, dy.shape[3]), []).append(i)
-    for mode in (3, 2, 1, 0):
-        idx = groups.get(mode)
-        if not idx:
-            continue
+    for i, j in enumerate(arr):
+        groups.setdefault(L.lib().pti_conv_wgrad_batched_mode(j.n, j.h, j.w, j.cin, j.cout), []).append(i)
+    for mode in sorted(groups, reverse=True):
+        idx = groups[mode]
         sub = (L.WgradJob * len(idx))(*[arr[i] for i in idx])
-        fl = sum(2.0 * jobs[i][0].shape[0] * jobs[i][0].shape[1] * jobs[i][0].shape[2] * jobs[i][1].shape[3] * jobs[i][0].shape[3] * 9
-                 for i in idx)
-        nb = sum(2.0 * (jobs[i][0].numel() + jobs[i][1].numel()) for i in idx)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+        rec = _prof_begin(prof)
         L.check(L.lib().pti_conv_wgrad_mfma_batched(sub, len(idx), _ptr(ws), ws.numel() * 4, _stream()),
                 "pti_conv_wgrad_mfma_batched")
-        e1.record()
-        prof.append((last_kernel_name(), fl, nb, e0, e1, ("conv wgrad (batched)", 0, 0, 0, 0, 3, "s1", len(idx))))
+        _prof_end(rec, sum(2.0 * arr[i].n * arr[i].h * arr[i].w * arr[i].cout * arr[i].cin * 9 for i in idx),
+                  sum(2.0 * (jobs[i][0].numel() + jobs[i][1].numel()) for i in idx),
+                  ("conv wgrad (batched)", 0, 0, 0, 0, 3, "s1", len(idx)))
 
 
 def gn_bwd(x, da, dx, stats, gamma, beta, sums, dgamma, dbeta, *, groups, eps=1e-6, silu=True, dres=None):
@@ -459,20 +476,15 @@ def conv_mfma_gnbwd(dy_in, w_packed_t, gx, gstats, ggamma, gbeta, dy_out, gsums,
         raise ValueError("conv_mfma_gnbwd: unsupported shape")
     part = torch.empty(n * tiles * cout * 2, dtype=torch.float32, device=dy_in.device)
     prof = KERNEL_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    rec = None if prof is None else _prof_begin(prof)
     L.check(L.lib().pti_conv2d_mfma_gnbwd(_ptr(dy_in), _ptr(w_packed_t), _ptr(gx), _ptr(gstats), _ptr(ggamma),
                                           _ptr(gbeta), _ptr(dy_out), _ptr(part), C.byref(d), int(silu), _stream()),
             "pti_conv2d_mfma_gnbwd")
-    if prof is not None:
-        e1.record()
-        name = last_kernel_name()
+    if rec is not None:     # (the finalize launch is not part of the record)
+        _prof_end(rec, 2.0 * n * ho * wo * cout * cin * ksize * ksize * (0.25 if mode == PTI_CONV_ZINS else 1.0),
+                  2.0 * (dy_in.numel() + 2 * dy_out.numel()),
+                  ("conv dgrad+GN bwd", cin, cout, ho, wo, ksize, "zins" if mode == PTI_CONV_ZINS else "s1", n))
     L.check(L.lib().pti_gn_sums_finalize(_ptr(part), _ptr(gsums), n, tiles, 2 * cout, _stream()), "pti_gn_sums_finalize")
-    if prof is not None:
-        prof.append((name, 2.0 * n * ho * wo * cout * cin * ksize * ksize * (0.25 if mode == PTI_CONV_ZINS else 1.0),
-                     2.0 * (dy_in.numel() + 2 * dy_out.numel()), e0, e1,
-                     ("conv dgrad+GN bwd", cin, cout, ho, wo, ksize, "zins" if mode == PTI_CONV_ZINS else "s1", n)))
     return dy_out
 
 
@@ -510,24 +522,19 @@ def conv_mfma_gnbwd_chain(g_in, x_in, in_stats, in_gamma, in_sums, dx_in, w_pack
         raise ValueError("conv_mfma_gnbwd_chain: unsupported shape")
     part = torch.empty(n * tiles * cout * 2, dtype=torch.float32, device=g_in.device)
     prof = KERNEL_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    rec = None if prof is None else _prof_begin(prof)
     L.check(L.lib().pti_conv2d_mfma_gnbwd_chain(_ptr(g_in), _ptr(x_in), int(x_in.dtype == F16), _ptr(in_stats), _ptr(in_gamma),
                                                 _ptr(in_sums), _ptr(dx_in), _ptr(w_packed_t), _ptr(gx), _ptr(gstats),
                                                 _ptr(ggamma), _ptr(gbeta), _ptr(dy_out), _ptr(part), C.byref(d), int(silu),
                                                 _stream()), "pti_conv2d_mfma_gnbwd_chain")
-    if prof is not None:
-        e1.record()
-        name = last_kernel_name()
+    if rec is not None:     # reads g, x_in, gx; writes dx_in and dy_out (the finalize launch is not part of the record)
+        _prof_end(rec, 2.0 * n * h * w * cout * cin * 9, 2.0 * (3 * g_in.numel() + 2 * dy_out.numel()),
+                  ("conv dgrad+GN bwd (chained)", cin, cout, h, w, 3, "s1", n))
     if in_dgamma is not None or in_dbeta is not None:
         L.check(L.lib().pti_gn_sums_finalize_affine(_ptr(part), _ptr(gsums), n, tiles, 2 * cout, _ptr(in_sums), _ptr(in_dgamma),
                                                     _ptr(in_dbeta), cin, _stream()), "pti_gn_sums_finalize_affine")
     else:
         L.check(L.lib().pti_gn_sums_finalize(_ptr(part), _ptr(gsums), n, tiles, 2 * cout, _stream()), "pti_gn_sums_finalize")
-    if prof is not None:     # reads g, x_in, gx; writes dx_in and dy_out
-        prof.append((name, 2.0 * n * h * w * cout * cin * 9, 2.0 * (3 * g_in.numel() + 2 * dy_out.numel()), e0, e1,
-                     ("conv dgrad+GN bwd (chained)", cin, cout, h, w, 3, "s1", n)))
     return dy_out
 
 
@@ -545,16 +552,13 @@ def gn_bwd_apply(x, dy, dx, stats, gamma, beta, sums, dgamma, dbeta, *, groups, 
         raise ValueError("gn_bwd_apply: shape mismatch")
     _chk_stats(stats, n * groups * 2, "stats")
     prof = KERNEL_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    rec = None if prof is None else _prof_begin(prof)
     L.check(L.lib().pti_gn_bwd_apply(_ptr(x), _ptr(dy), _ptr(dres), _ptr(dx), _ptr(stats), _ptr(gamma), _ptr(beta),
                                      _ptr(sums), _ptr(dgamma), _ptr(dbeta), n, h * w, c, groups, eps,
                                      int(x.dtype == F16), _stream()), "pti_gn_bwd_apply")
-    if prof is not None:   # pure HBM pass: reads x, dy (+ dres), writes dx; ~8 flops per element
-        e1.record()
-        prof.append((last_kernel_name(), 8.0 * x.numel(), 2.0 * x.numel() * (4 if dres is not None else 3), e0, e1,
-                     ("GroupNorm bwd apply", c, c, h, w, 0, "-", n)))
+    if rec is not None:   # pure HBM pass: reads x, dy (+ dres), writes dx; ~8 flops per element
+        _prof_end(rec, 8.0 * x.numel(), 2.0 * x.numel() * (4 if dres is not None else 3),
+                  ("GroupNorm bwd apply", c, c, h, w, 0, "-", n))
     return dx
 
 
@@ -599,11 +603,6 @@ def post_quant_bwd(dzq, z_nchw, wp, dz, gwp, gbp):
     ws = torch.empty(POST_QUANT_BWD_MAX_BLOCKS * (l * l + l), dtype=torch.float32, device=dzq.device)
     L.check(L.lib().pti_post_quant_bwd(_ptr(dzq), _ptr(z_nchw), _ptr(wp), _ptr(dz), _ptr(gwp), _ptr(gbp), _ptr(ws), b, hw, l,
                                        _stream()), "pti_post_quant_bwd")
-
-
-LATENT_BWD_MAX_BLOCKS = 512   # PTI_LATENT_BWD_MAX_BLOCKS / PTI_VAE_LOSS_MAX_BLOCKS of include/pti_vae.h
-VAE_LOSS_MAX_BLOCKS = 1024
-POST_QUANT_BWD_MAX_BLOCKS = 256
 
 
 def latent_head_bwd(h, eps, wm, bm, wl, bl, wp, bp, dzq, dmu, dsigma, dh, gwm, gbm, gwl, gbl, gwp, gbp):
@@ -759,7 +758,6 @@ def preprocess_batch(src, offsets, hw, out, stats=None):
 # ---- evaluation metrics (csrc/image_metrics.hip; include/pti_vae.h "evaluation metrics") ------------------------------
 SSIM_WINDOW, SSIM_SIGMA = 11, 1.5
 _ssim_taps = None
-_metrics_ws = {}
 
 
 def ssim_taps() -> torch.Tensor:
@@ -793,17 +791,9 @@ def image_metrics(pred, target, *, clamp=None, data_range=1.0, k1=0.01, k2=0.03,
     floats = L.lib().pti_image_metrics_ws_floats(n, c, h, w)
     if floats <= 0:
         raise ValueError(f"image_metrics: unsupported shape {tuple(pred.shape)}")
-    if out is None:
-        out = torch.empty(n, 4, dtype=F32, device=pred.device)
-    else:
-        _chk(out, F32, "out", 2)
-        if tuple(out.shape) != (n, 4) or out.device != pred.device:
-            raise ValueError(f"image_metrics: out must be [{n}, 4] on {pred.device}")
+    out = _out(out, (n, 4), F32, pred.device, "image_metrics: out", chk_name="out")
     stream = _stream()
-    key = (pred.device.index, stream, n, c, h, w)
-    ws = _metrics_ws.get(key)
-    if ws is None:
-        ws = _metrics_ws[key] = torch.empty(floats, dtype=F32, device=pred.device)
+    ws = _scratch("metrics", (n, c, h, w), floats, pred.device, stream)
     lo, hi = (0.0, 0.0) if clamp is None else (float(clamp[0]), float(clamp[1]))
     L.check(L.lib().pti_image_metrics(_ptr(pred), _ptr(target), n, c, h, w, int(clamp is not None), lo, hi, float(data_range),
                                       float(k1), float(k2), C.c_void_p(ssim_taps().data_ptr()), _ptr(out), _ptr(ws), stream),
@@ -812,9 +802,6 @@ def image_metrics(pred, target, *, clamp=None, data_range=1.0, k1=0.01, k2=0.03,
 
 
 # ---- latent-space analysis (csrc/latent_stats.hip; include/pti_vae.h "latent-space analysis") -------------------------
-_latent_ws = {}
-
-
 def _rows(t, name):
     """-> ``t`` as an fp32 device matrix whose rows are dense (column stride 1, row stride >= columns); a view that
     already is one (a row-strided slice included) is passed through without a copy."""
@@ -832,6 +819,7 @@ def _rows(t, name):
 
 
 def _latent_out(out, shape, like, name):
+    """Not _out: a view with a row stride is written in place, so the rule is dense rows, not contiguity."""
     if out is None:
         return torch.empty(shape, dtype=F32, device=like.device)
     if not isinstance(out, torch.Tensor) or not out.is_cuda:
@@ -841,14 +829,6 @@ def _latent_out(out, shape, like, name):
     if tuple(out.shape) != tuple(shape) or out.device != like.device or out.stride(1) != 1 or out.stride(0) < shape[1]:
         raise ValueError(f"{name}: out must be {list(shape)} on {like.device} with dense rows")
     return out
-
-
-def _latent_workspace(kind, shape, floats, device, stream):
-    key = (kind, device.index, stream) + tuple(shape)
-    ws = _latent_ws.get(key)
-    if ws is None:
-        ws = _latent_ws[key] = torch.empty(floats, dtype=F32, device=device)
-    return ws
 
 
 def latent_pairwise(a, b=None, *, mode="dist", center=None, out=None):
@@ -879,7 +859,7 @@ def latent_pairwise(a, b=None, *, mode="dist", center=None, out=None):
         raise ValueError(f"latent_pairwise: unsupported shape a {tuple(a.shape)} b {tuple(b.shape)}")
     out = _latent_out(out, (n1, n2), a, "latent_pairwise")
     stream = _stream()
-    ws = _latent_workspace("pair", (n1, n2, d), floats, a.device, stream)
+    ws = _scratch("pair", (n1, n2, d), floats, a.device, stream)
     L.check(L.lib().pti_latent_pairwise(_ptr(a), a.stride(0), n1, _ptr(b), b.stride(0), n2, d, _ptr(center),
                                         int(mode == "dot"), _ptr(out), out.stride(0), _ptr(ws), stream), "pti_latent_pairwise")
     return out
@@ -913,7 +893,7 @@ def latent_group_stats(a, seg_a, b, seg_b, *, out=None):
     if out.stride(0) != 4:
         raise ValueError("latent_group_stats: out must be contiguous")
     stream = _stream()
-    ws = _latent_workspace("group", (n1, n2, e, d), floats, a.device, stream)
+    ws = _scratch("group", (n1, n2, e, d), floats, a.device, stream)
     L.check(L.lib().pti_latent_group_stats(_ptr(a), a.stride(0), n1, _ptr(seg_a), _ptr(b), b.stride(0), n2, _ptr(seg_b), e, d,
                                            _ptr(out), _ptr(ws), stream), "pti_latent_group_stats")
     return out
@@ -963,15 +943,11 @@ def mask_geometry(src, offsets, hw, *, elem, max_h, sample_rows, bottom_offsets,
     samples, n_bottom = sample_rows.shape[1], bottom_offsets.numel()
     shapes = ((b, 4), (b, samples), (b, n_bottom))
     if out is None:
-        out = tuple(torch.empty(sh, dtype=torch.int32, device=src.device) for sh in shapes)
-    else:   # caller-owned outputs (views of larger buffers included)
-        if len(out) != 3:
-            raise ValueError("mask_geometry: out must be (bbox, bbox_widths, bottom_widths)")
-        for name, t, sh in zip(("bbox", "bbox_widths", "bottom_widths"), out, shapes):
-            _chk(t, torch.int32, f"mask_geometry: out {name}")
-            if tuple(t.shape) != sh or t.device != src.device:
-                raise ValueError(f"mask_geometry: out {name} must be {list(sh)} on {src.device}")
-    bbox, bbox_widths, bottom_widths = out
+        out = (None, None, None)
+    elif len(out) != 3:   # caller-owned outputs (views of larger buffers included)
+        raise ValueError("mask_geometry: out must be (bbox, bbox_widths, bottom_widths)")
+    bbox, bbox_widths, bottom_widths = (_out(t, sh, torch.int32, src.device, f"mask_geometry: out {name}", rank=False)
+                                        for name, t, sh in zip(("bbox", "bbox_widths", "bottom_widths"), out, shapes))
     # a table or an output without entries is passed as NULL
     L.check(L.lib().pti_mask_geometry(_ptr(src), _ptr(offsets), _ptr(hw), b, elem, max_h,
                                       _ptr(sample_rows) if samples else None, samples,
@@ -1022,6 +998,21 @@ def pd_in_stats(y, eps=1e-5, table=None):
     return table
 
 
+def _pd_norm_sums(norm, g, launch):
+    """Shared tail of pd_col2im / pd_final_dgrad, whose kernels write ``g`` [n, h, w, c]: ``launch(part)`` with the block
+    partials of the InstanceNorm-backward sums (None without ``norm``), then their fixed-order fold by
+    pti_gn_sums_finalize -> sums [n, c, 2] | None."""
+    n, h, w, c = g.shape
+    if norm is None:
+        launch(None)
+        return None
+    part = torch.empty(n, L.lib().pti_pd_col2im_blocks(n, h * w, c), c, 2, dtype=F32, device=g.device)
+    launch(part)
+    sums = torch.empty(n, c, 2, dtype=F32, device=g.device)
+    L.check(L.lib().pti_gn_sums_finalize(_ptr(part), _ptr(sums), n, part.shape[1], 2 * c, _stream()), "pti_gn_sums_finalize")
+    return sums
+
+
 def pd_col2im(d_patches, y_prev, norm, g, *, stride, slope=0.2):
     """-> (g, sums [n,c,2] | None): g = LeakyReLU'(norm(y_prev)) * col2im(d_patches); with ``norm`` also the
     InstanceNorm-backward sums {sum g, sum g*xhat} (block partials folded in fixed order by pti_gn_sums_finalize)."""
@@ -1032,17 +1023,11 @@ def pd_col2im(d_patches, y_prev, norm, g, *, stride, slope=0.2):
     ho, wo = pd_out_hw(h, w, stride)
     if tuple(d_patches.shape) != (n, ho, wo, 16 * c) or g.shape != y_prev.shape:
         raise ValueError(f"pd_col2im: d_patches {tuple(d_patches.shape)} for y_prev {tuple(y_prev.shape)} stride {stride}")
-    part = sums = None
     if norm is not None:
         _chk(norm, F32, "norm")
-        bps = L.lib().pti_pd_col2im_blocks(n, h * w, c)
-        part = torch.empty(n, bps, c, 2, dtype=F32, device=g.device)
-    L.check(L.lib().pti_pd_col2im(_ptr(d_patches), _ptr(y_prev), _ptr(norm), _ptr(g), _ptr(part), n, h, w, c, stride,
-                                  float(slope), _stream()), "pti_pd_col2im")
-    if part is not None:
-        sums = torch.empty(n, c, 2, dtype=F32, device=g.device)
-        L.check(L.lib().pti_gn_sums_finalize(_ptr(part), _ptr(sums), n, part.shape[1], 2 * c, _stream()), "pti_gn_sums_finalize")
-    return g, sums
+    return g, _pd_norm_sums(norm, g, lambda part: L.check(
+        L.lib().pti_pd_col2im(_ptr(d_patches), _ptr(y_prev), _ptr(norm), _ptr(g), _ptr(part), n, h, w, c, stride,
+                              float(slope), _stream()), "pti_pd_col2im"))
 
 
 def pd_col2im_image(d_patches, d_img, *, scale=1.0, accumulate=False):
@@ -1105,15 +1090,9 @@ def pd_final_dgrad(d_logits, y_prev, norm, w16c, g, *, slope=0.2):
     n, h, w, c = y_prev.shape
     if d_logits.numel() != n * (h - 1) * (w - 1) or g.shape != y_prev.shape or w16c.numel() != 16 * c:
         raise ValueError("pd_final_dgrad: shapes")
-    part = sums = None
-    if norm is not None:
-        part = torch.empty(n, L.lib().pti_pd_col2im_blocks(n, h * w, c), c, 2, dtype=F32, device=g.device)
-    L.check(L.lib().pti_pd_final_dgrad(_ptr(d_logits), _ptr(y_prev), _ptr(norm), _ptr(w16c), _ptr(g), _ptr(part), n, h, w, c,
-                                       float(slope), _stream()), "pti_pd_final_dgrad")
-    if part is not None:
-        sums = torch.empty(n, c, 2, dtype=F32, device=g.device)
-        L.check(L.lib().pti_gn_sums_finalize(_ptr(part), _ptr(sums), n, part.shape[1], 2 * c, _stream()), "pti_gn_sums_finalize")
-    return g, sums
+    return g, _pd_norm_sums(norm, g, lambda part: L.check(
+        L.lib().pti_pd_final_dgrad(_ptr(d_logits), _ptr(y_prev), _ptr(norm), _ptr(w16c), _ptr(g), _ptr(part), n, h, w, c,
+                                   float(slope), _stream()), "pti_pd_final_dgrad"))
 
 
 def pd_final_wgrad(d_logits, y_prev, norm, *, slope=0.2):
@@ -1339,7 +1318,6 @@ def squeeze_conv1_bwd(g, t0, w10, h, w):
 MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_OUT = 8, 1024, 64    # PTI_MLP_MAX_* of include/pti_vae.h
 MLP_ACTS = ("relu", "gelu", "leaky_relu", "elu")            # activation codes 0 .. 3 of pti_mlp_head_fwd
 MLP_LOSSES = {"mse": 0, "mse_loss": 0, "smooth_l1": 1, "huber": 1}
-_mlp_ws = {}
 
 
 def mlp_head_pack(regressor):
@@ -1432,29 +1410,14 @@ def mlp_head_fwd(x, params, dims, act, *, mean=None, std=None, targets=None, los
         _chk(targets, F32, "mlp_head_fwd: targets", 2)
         if tuple(targets.shape) != (n, t_out) or targets.device != x.device:
             raise ValueError(f"mlp_head_fwd: targets must be [{n}, {t_out}] on {x.device}")
-    if pred is None:
-        pred = torch.empty(n, t_out, dtype=F32, device=x.device)
-    else:
-        _chk(pred, F32, "mlp_head_fwd: pred", 2)
-        if tuple(pred.shape) != (n, t_out) or pred.device != x.device:
-            raise ValueError(f"mlp_head_fwd: pred must be [{n}, {t_out}] on {x.device}")
-    if targets is None:
-        rowloss = None
-    elif rowloss is None:
-        rowloss = torch.empty(n, dtype=F32, device=x.device)
-    else:
-        _chk(rowloss, F32, "mlp_head_fwd: rowloss", 1)
-        if rowloss.numel() != n or rowloss.device != x.device:
-            raise ValueError(f"mlp_head_fwd: rowloss must be [{n}] on {x.device}")
+    pred = _out(pred, (n, t_out), F32, x.device, "mlp_head_fwd: pred")
+    rowloss = None if targets is None else _out(rowloss, (n,), F32, x.device, "mlp_head_fwd: rowloss")
     arr = _dims_array(dims)
     floats = L.lib().pti_mlp_head_ws_floats(n, d, arr, len(dims) - 1)
     if floats <= 0:
         raise ValueError(f"mlp_head_fwd: unsupported shape x {tuple(x.shape)} head {dims}")
     stream = _stream()
-    key = (x.device.index, stream, n, d, dims[1])
-    ws = _mlp_ws.get(key)
-    if ws is None:
-        ws = _mlp_ws[key] = torch.empty(floats, dtype=F32, device=x.device)
+    ws = _scratch("mlp", (n, d, dims[1]), floats, x.device, stream)
     L.check(L.lib().pti_mlp_head_fwd(_ptr(x), x.stride(0), n, d, _ptr(params), arr, len(dims) - 1, int(act), _ptr(mean),
                                      _ptr(std), _ptr(targets), MLP_LOSSES[loss], _ptr(pred), _ptr(rowloss), _ptr(ws), stream),
             "pti_mlp_head_fwd")
@@ -1502,12 +1465,7 @@ def elastic_field(keys, alpha, sigma, h, w, out=None):
     if radius > min(h, w) or radius > ELASTIC_MAX_RADIUS:
         raise ValueError(f"elastic_field: radius {radius} of sigma {sigma} must not exceed min(h, w) = {min(h, w)} "
                          f"nor {ELASTIC_MAX_RADIUS}")
-    if out is None:
-        out = torch.empty(b, 2, h, w, dtype=F32, device=keys.device)
-    else:
-        _chk(out, F32, "elastic_field: out", 4)
-        if tuple(out.shape) != (b, 2, h, w) or out.device != keys.device:
-            raise ValueError(f"elastic_field: out must be [{b}, 2, {h}, {w}] on {keys.device}")
+    out = _out(out, (b, 2, h, w), F32, keys.device, "elastic_field: out")
     L.check(L.lib().pti_elastic_field(_ptr(keys), _ptr(alpha), sigma, b, h, w, _ptr(out), _stream()), "pti_elastic_field")
     return out
 
@@ -1527,11 +1485,6 @@ def augment_warp(src, mat, field=None, out=None):
         _chk(field, F32, "augment_warp: field", 4)
         if tuple(field.shape) != (b, 2, h, w) or field.device != src.device:
             raise ValueError(f"augment_warp: field must be [{b}, 2, {h}, {w}] on {src.device}")
-    if out is None:
-        out = torch.empty_like(src)
-    else:
-        _chk(out, F32, "augment_warp: out", 4)
-        if out.shape != src.shape or out.device != src.device:
-            raise ValueError("augment_warp: out must have the shape and device of src")
+    out = _out(out, src.shape, F32, src.device, "augment_warp: out", msg="augment_warp: out must have the shape and device of src")
     L.check(L.lib().pti_augment_warp(_ptr(src), _ptr(mat), _ptr(field), b, c, h, w, _ptr(out), _stream()), "pti_augment_warp")
     return out

@@ -90,6 +90,29 @@ def test_tile_and_block_queries_need_no_gpu():
     assert lib.pti_gn_bwd_blocks(2, 64 * 64, 1024) == 0                         # above the kernel's channel cap
 
 
+def test_batched_wgrad_mode_query_needs_no_gpu(monkeypatch):
+    """pti_conv_wgrad_batched_mode: the kernel mode pti_conv_wgrad_mfma_batched files a job under (the rule lives in
+    csrc/wgrad_mfma.hip alone), as pure host arithmetic.  PTI_WGRAD_V6 is read per call."""
+    from pti_ldm_vae_amd import _lib as L
+    mode = L.lib().pti_conv_wgrad_batched_mode
+    monkeypatch.delenv("PTI_WGRAD_V6", raising=False)
+    assert mode(2, 32, 32, 32, 32) == 0            # pairs of 32 x 32 tiles
+    assert mode(2, 32, 32, 32, 64) == 1            # two output-channel blocks per workgroup
+    assert mode(2, 32, 32, 64, 128) == 2           # v6 shape A
+    assert mode(2, 32, 32, 64, 64) == 3            # v6 shape B ...
+    assert mode(2, 256, 256, 64, 64) == 1          # ... by default only on maps of at most 128 x 128 pixels
+    assert mode(2, 32, 32, 48, 32) < 0             # channels not a multiple of 32: not eligible
+    monkeypatch.setenv("PTI_WGRAD_V6", "0")
+    assert mode(2, 32, 32, 64, 128) == 1
+    monkeypatch.setenv("PTI_WGRAD_V6", "2")
+    assert mode(2, 256, 256, 64, 64) == 3
+
+
+def test_ops_does_not_mirror_the_wgrad_mode_rule():
+    text = open(os.path.join(ROOT, "pti_ldm_vae_amd", "ops.py")).read()
+    assert "PTI_WGRAD_V6" not in text and "PTI_WGRAD_V4_COB2" not in text
+
+
 def test_entry_points_refuse_wrong_result_environment(monkeypatch):
     """no ``PTI_DIAG_*`` knob lives in the product any more; what is left (a native tuning aid that
     needs PTI_ALLOW_WRONG_RESULTS=1 as a second opt-in) makes bench.py and train_vae.py exit before touching the GPU."""
