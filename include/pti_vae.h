@@ -36,7 +36,8 @@ typedef void* pti_stream_t; /* hipStream_t */
                                for pti_mask_geometry, appended after those.
                                Still 5: pti_mlp_head_fwd / pti_mlp_head_ws_floats / pti_regression_metrics, appended after
                                pti_mask_geometry in the same way.
-                               Still 5: pti_conv_wgrad_batched_mode (a host-only query) appended in the same way. */
+                               Still 5: pti_conv_wgrad_batched_mode (a host-only query) appended in the same way.
+                               Still 5: pti_tsne_affinities / pti_tsne_step (+ their _ws_floats) appended in the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -576,6 +577,36 @@ int pti_elastic_field(const uint64_t* keys, const float* alpha, float sigma, int
                       pti_stream_t s);
 int pti_augment_warp(const float* src, const float* mat, const float* field, int b, int c, int h, int w, float* out,
                      pti_stream_t s);
+
+/* ---- exact t-SNE of the latent-space analysis (sklearn.manifold._t_sne: _joint_probabilities, _kl_divergence,
+ *      _gradient_descent; csrc/tsne.hip) ----
+ * Dense O(n^2) t-SNE with one degree of freedom into TWO columns, 2 <= n <= 8192.  No atomics; every sum has one order
+ * that depends on n only, so results are bitwise reproducible.  Matrices are fp32 row-major with a row stride in ELEMENTS
+ * (ldd, ldp >= n).  Refused before any launch: null pointers, n < 2, a row stride below n, a perplexity outside (0, n),
+ * exaggeration <= 0, misaligned fp64 buffers, y_out == y_in, p == d2 (PTI_EINVAL); n > 8192, n_components != 2
+ * (PTI_EUNSUPPORTED).
+ * pti_tsne_affinities: d2 = SQUARED Euclidean distances [n][n].  Per row sklearn's _binary_search_perplexity in fp64 (beta
+ *   from 1, at most 100 steps, tolerance 1e-5f on the entropy, p_ii = 0, a zero row sum replaced by 1e-8f), then
+ *   p[i][j] = max((p_j|i + p_i|j) / S, 2.220446e-16) with S the fp64 sum of the symmetrised matrix, 0 on the diagonal:
+ *   symmetric bit for bit.  plogp2: two DEVICE doubles {sum_ij p log p, sum_ij p}.  p doubles as the scratch of the
+ *   conditional probabilities.  workspace: pti_tsne_affinities_ws_floats(n) floats, 8-byte aligned.
+ * pti_tsne_step: one iteration of sklearn's _gradient_descent on y_in -> y_out (fp32 [n][2], two distinct buffers), update
+ *   and gains (fp32 [n][2]) in place: num_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} num_ij,
+ *   grad_i = 4 (exaggeration * sum_j p_ij num_ij (y_i - y_j) - sum_j num_ij^2 (y_i - y_j) / Z); gain += 0.2 where update and
+ *   grad have opposite signs, *= 0.8 elsewhere, floored at 0.01; update = momentum * update - lr * gain * grad;
+ *   y_out = y_in + update.  record: two DEVICE doubles, written only when with_record != 0 (the sum behind the KL value is
+ *   fp64 work and one more single-wavefront launch folds the norm; sklearn, too, evaluates both only where it reads them):
+ *   record[0] = KL(exaggeration * p || q) at y_in (q is not clamped at 2.2e-16 as sklearn's is); record[1] =
+ *   |gain * grad|_2, the norm sklearn's stopping rule tests.  plogp2: as written by pti_tsne_affinities.
+ *   workspace: pti_tsne_step_ws_floats(n, n_components) floats, 8-byte aligned.
+ * Both *_ws_floats are pure host arithmetic; 0 = unsupported shape.                                                      */
+int64_t pti_tsne_affinities_ws_floats(int n);
+int pti_tsne_affinities(const float* d2, int64_t ldd, int n, float perplexity, float* p, int64_t ldp, double* plogp2,
+                        float* workspace, pti_stream_t s);
+int64_t pti_tsne_step_ws_floats(int n, int n_components);
+int pti_tsne_step(const float* p, int64_t ldp, int n, int n_components, const float* y_in, float* y_out, float* update,
+                  float* gains, const double* plogp2, float exaggeration, float momentum, float lr, double* record,
+                  int with_record, float* workspace, pti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -165,6 +165,10 @@ SIGNATURES = {
     "pti_regression_metrics": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "pti_elastic_field": (_I, [_P, _P, _F, _I, _I, _I, _P, _P]),
     "pti_augment_warp": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "pti_tsne_affinities_ws_floats": (_I64, [_I]),
+    "pti_tsne_affinities": (_I, [_P, _I64, _I, _F, _P, _I64, _P, _P, _P]),
+    "pti_tsne_step_ws_floats": (_I64, [_I, _I]),
+    "pti_tsne_step": (_I, [_P, _I64, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _P, _I, _P, _P]),
 }
 
 _lib = None

@@ -4,8 +4,9 @@ error texts and output files).
 What differs is where the arithmetic runs.  The latents of all images stay on the device as one ``[N, D]`` matrix
 (D = 4 096 .. 40 960); the per-patient distance statistics of all patients come out of ONE ``ops.latent_group_stats``
 call, and PCA takes the centred Gram matrix ``Xc Xc^T`` from ``ops.latent_pairwise(mode="dot", center=mean)`` and
-diagonalises that N x N matrix in fp64 on the host.  Only results cross to the host.  t-SNE and UMAP remain host
-libraries fed with the PCA output."""
+diagonalises that N x N matrix in fp64 on the host.  Only results cross to the host.  UMAP and the default t-SNE are
+host libraries fed with the PCA output; ``reduce_dimensionality_tsne(backend="hip")`` is exact t-SNE on the device
+(``ops.tsne_affinities`` / ``ops.tsne_step``, csrc/tsne.hip)."""
 from __future__ import annotations
 
 import os
@@ -238,20 +239,91 @@ class LatentSpaceAnalyzer:
         return model.fit_transform(vectors_pca), model
 
     def reduce_dimensionality_tsne(self, latent_vectors, n_components: int = 2, perplexity: int = 30, random_state: int = 42,
-                                   pca_components: int = 50) -> np.ndarray:
-        """PCA, then t-SNE on the host -> reduced ``[N, n_components]``."""
+                                   pca_components: int = 50, backend: str = "sklearn", max_iter: int = 1000,
+                                   exploration_n_iter: int = 250, early_exaggeration: float = 12.0) -> np.ndarray:
+        """PCA, then t-SNE -> reduced ``[N, n_components]`` fp64 on the host.
+
+        ``backend="sklearn"``: ``sklearn.manifold.TSNE(init="pca")`` on the host (Barnes-Hut); the last three parameters
+        are not used.  ``backend="hip"``: exact t-SNE on the device (``ops.tsne_affinities`` / ``ops.tsne_step``) with
+        sklearn's schedule and defaults, no host library; ``n_components`` must be 2 and N at most 8192.  It starts from
+        the first two principal components scaled to a standard deviation of 1e-4, ``random_state`` is accepted and
+        unused: the result is a pure function of the input, bit for bit.  The last KL value is kept in
+        ``self.tsne_kl_divergence_``."""
+        if backend not in ("sklearn", "hip"):
+            raise ValueError(f"backend must be 'sklearn' or 'hip', got {backend!r}")
         n_samples = self._check_reduction_input(latent_vectors, pca_components)
         if perplexity >= n_samples:
             raise ValueError(f"perplexity ({perplexity}) must be < n_samples ({n_samples}). "
                              f"Reduce perplexity or provide more samples.")
         if perplexity < 5:
             print(f"Warning: perplexity={perplexity} is very low. Consider using 5-50 for better results.")
+        if backend == "hip":
+            if n_components != 2:
+                raise ValueError(f"backend='hip' computes n_components=2 only, got {n_components}")
+            vectors_pca, _ = self.reduce_dimensionality_pca(latent_vectors, pca_components)
+            return self._tsne_device(vectors_pca, perplexity, max_iter, exploration_n_iter, early_exaggeration)
         try:
             from sklearn.manifold import TSNE
         except ImportError as e:
             raise ImportError("Please install scikit-learn: pip install scikit-learn") from e
         vectors_pca, _ = self.reduce_dimensionality_pca(latent_vectors, pca_components)
         return TSNE(n_components=n_components, perplexity=perplexity, init="pca", random_state=random_state).fit_transform(vectors_pca)
+
+    @staticmethod
+    def tsne_init(vectors_pca: np.ndarray) -> np.ndarray:
+        """sklearn's ``init="pca"`` for rows that are PCA projections already: their first two columns ARE their principal
+        axes; scaled to a population std of 1e-4 in column 0, rounded to fp32 -> ``[N, 2]`` fp32."""
+        y = np.zeros((len(vectors_pca), 2))
+        y[:, :min(2, vectors_pca.shape[1])] = vectors_pca[:, :2]
+        std = float(y[:, 0].std())
+        return (y / std * 1e-4 if std > 0 else y).astype(np.float32)
+
+    def tsne_descend(self, p: torch.Tensor, sums: torch.Tensor, y0: torch.Tensor, max_iter: int = 1000,
+                     exploration_n_iter: int = 250, early_exaggeration: float = 12.0) -> tuple[torch.Tensor, float]:
+        """sklearn 1.7's ``TSNE._tsne`` schedule (``learning_rate="auto"``) on the device -> (Y fp32 [N, 2] on the device,
+        KL at that Y; also kept in ``self.tsne_kl_divergence_``).  Momentum 0.5 with exaggeration for ``exploration_n_iter``
+        iterations, then 0.8 without up to ``max_iter``.  Two launches per iteration, enqueued in order on the current
+        stream; every 50th iteration also writes the two-double record {KL, gradient norm}, which then comes to the host
+        for sklearn's stopping rule: |grad| <= 1e-7, or no KL improvement for more than ``exploration_n_iter`` (stage 1) /
+        300 (stage 2) iterations.  The returned KL is evaluated at the returned Y by one more force pass (sklearn's
+        ``kl_divergence_`` is the value one update earlier)."""
+        from .. import ops
+        n = p.shape[0]
+        lr = max(n / early_exaggeration / 4.0, 50.0)
+        y = [y0.to(torch.float32).contiguous().clone(), torch.empty(n, 2, dtype=torch.float32, device=p.device)]
+        update, gains = torch.zeros_like(y[0]), torch.ones_like(y[0])
+        record = torch.zeros(2, dtype=torch.float64, device=p.device)
+        it, cur = 0, 0
+        for stop, momentum, exaggeration, patience in ((min(exploration_n_iter, max_iter), 0.5, early_exaggeration, exploration_n_iter),
+                                                       (max_iter, 0.8, 1.0, 300)):
+            best, best_it = float("inf"), it
+            for i in range(it, stop):
+                check = (i + 1) % 50 == 0
+                ops.tsne_step(p, y[cur], y[cur ^ 1], update, gains, record, sums=sums, exaggeration=exaggeration,
+                              momentum=momentum, lr=lr, with_record=check)
+                cur ^= 1
+                it = i + 1
+                if check:
+                    kl, grad_norm = record.cpu().tolist()
+                    if kl < best:
+                        best, best_it = kl, i
+                    elif i - best_it > patience:
+                        break
+                    if grad_norm <= 1e-7:
+                        break
+        ops.tsne_step(p, y[cur], y[cur ^ 1], update.clone(), gains.clone(), record, sums=sums, exaggeration=1.0, momentum=0.8,
+                      lr=lr, with_record=True)                              # only its record is used
+        self.tsne_kl_divergence_ = record.cpu().tolist()[0]
+        return y[cur], self.tsne_kl_divergence_
+
+    def _tsne_device(self, vectors_pca: np.ndarray, perplexity: float, max_iter: int, exploration_n_iter: int,
+                     early_exaggeration: float) -> np.ndarray:
+        from .. import ops
+        dist = ops.latent_pairwise(self._to_device_matrix(vectors_pca))
+        p, sums = ops.tsne_affinities(dist.square_(), perplexity)
+        y, _ = self.tsne_descend(p, sums, torch.from_numpy(self.tsne_init(vectors_pca)).to(p.device), max_iter,
+                                 exploration_n_iter, early_exaggeration)
+        return y.cpu().double().numpy()
 
     # ---- colours ----
     def create_patient_colormap(self, patient_ids: list[str]) -> tuple[dict[str, int], dict[str, str]]:

@@ -4,7 +4,8 @@
     python -m pti_ldm_vae_amd.analyze_static --vae-weights W.pth --config-file CFG.json --folder-edente DIR [--folder-dente DIR]
 
 Same options and defaults, plus ``--method pca`` (the projection is the first two principal components; also the
-fallback, with a warning, when umap-learn / scikit-learn is not installed), ``--cache-dir`` and ``--batch-size``.
+fallback, with a warning, when umap-learn / scikit-learn is not installed), ``--cache-dir``, ``--batch-size`` and
+``--tsne-backend hip`` (``--method tsne`` as exact t-SNE on the device: deterministic, no host library).
 Outputs in ``--output-dir``: ``<method>_projection.png`` (matplotlib; ``.html`` through plotly when that fails),
 ``color_legend.txt`` with ``--color-by-patient``, and with two groups ``distance_metrics.txt``,
 ``exams_sorted_by_distance.txt`` and ``latents.npz`` (latents, ids, paths and projection of each group).
@@ -22,6 +23,13 @@ import torch
 from .analysis import LatentCache, LatentSpaceAnalyzer, load_image_paths
 
 
+class _Args(argparse.Namespace):
+    """The namespace ``parse_args`` fills.  ``--tsne-backend`` lives here as a class default and enters the instance only
+    when it is given, so a command line without it parses to exactly the attributes it always had."""
+
+    tsne_backend = "sklearn"
+
+
 def parse_args(argv=None) -> argparse.Namespace:
     parser = argparse.ArgumentParser(description="Static Latent Space Analysis (UMAP, t-SNE or PCA; MI355X, HIP engine)")
     parser.add_argument("--vae-weights", type=str, required=True, help="Path to VAE weights file")
@@ -37,12 +45,15 @@ def parse_args(argv=None) -> argparse.Namespace:
     parser.add_argument("--n-neighbors", type=int, default=40, help="UMAP n_neighbors parameter")
     parser.add_argument("--min-dist", type=float, default=0.5, help="UMAP min_dist parameter")
     parser.add_argument("--perplexity", type=int, default=30, help="t-SNE perplexity parameter")
+    parser.add_argument("--tsne-backend", type=str, choices=["sklearn", "hip"], default=argparse.SUPPRESS,
+                        help="t-SNE implementation: sklearn (host, Barnes-Hut; default) or hip (exact, on the device, "
+                             "deterministic, needs no host library)")
     parser.add_argument("--seed", type=int, default=42, help="Random seed for reproducibility")
     parser.add_argument("--subtitle", type=str, default=None, help="Optional subtitle for the plot")
     parser.add_argument("--dpi", type=int, default=300, help="DPI for output PNG (default: 300)")
     parser.add_argument("--cache-dir", type=str, default="cache/latents", help="Root of the per-image latent cache")
     parser.add_argument("--batch-size", type=int, default=8, help="Images per encoder call (default: 8)")
-    return parser.parse_args(argv)
+    return parser.parse_args(argv, namespace=_Args())
 
 
 class TiffPreprocess:
@@ -88,9 +99,11 @@ def project(analyzer: LatentSpaceAnalyzer, latents: np.ndarray, args: argparse.N
             if args.method == "umap":
                 return analyzer.reduce_dimensionality_umap(latents, n_neighbors=args.n_neighbors, min_dist=args.min_dist,
                                                            random_state=args.seed, pca_components=min(n, 50))[0], "umap"
-            print("(This may take a few minutes...)")
+            backend = getattr(args, "tsne_backend", "sklearn")       # a namespace built by hand may not carry it
+            if backend == "sklearn":
+                print("(This may take a few minutes...)")
             return analyzer.reduce_dimensionality_tsne(latents, perplexity=args.perplexity, random_state=args.seed,
-                                                       pca_components=min(n, 50)), "tsne"
+                                                       pca_components=min(n, 50), backend=backend), "tsne"
         except ImportError as e:
             print(f"[WARN] --method {args.method} is not available ({e}); falling back to --method pca")
     if n < 2:

@@ -899,6 +899,78 @@ def latent_group_stats(a, seg_a, b, seg_b, *, out=None):
     return out
 
 
+# ---- exact t-SNE (csrc/tsne.hip; include/pti_vae.h "exact t-SNE") -------------------------------------------------------
+def _tsne_matrix(t, name):
+    """An fp32 device matrix [n, n] with dense rows, used in place (never copied: a copy would hide the caller's buffer)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
+    if t.dtype != F32:
+        raise TypeError(f"{name}: expected fp32, got {t.dtype}")
+    if t.dim() != 2 or t.shape[0] != t.shape[1] or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise ValueError(f"{name}: expected a square [n, n] matrix with dense rows, got {tuple(t.shape)}")
+    return t
+
+
+def tsne_affinities(d2, perplexity, *, out=None):
+    """Joint probabilities of exact t-SNE (``pti_tsne_affinities``) from the fp32 matrix ``d2`` [n, n] of SQUARED Euclidean
+    distances -> ``(P, sums)``: ``P`` fp32 [n, n], symmetric bit for bit with a zero diagonal (sklearn's
+    ``_joint_probabilities`` in dense form: the per-row perplexity search in fp64, then ``max((p_j|i + p_i|j) / S, eps)``),
+    and ``sums`` = the fp64 device pair ``{sum P log P, sum P}`` that ``tsne_step`` needs for the KL value.
+    2 <= n <= 8192, 0 < perplexity < n.  Runs on the current stream, no host sync."""
+    d2 = _tsne_matrix(d2, "tsne_affinities: d2")
+    n = d2.shape[0]
+    perplexity = float(perplexity)
+    if not 0.0 < perplexity < n:
+        raise ValueError(f"tsne_affinities: perplexity ({perplexity:g}) must be positive and < n ({n})")
+    floats = L.lib().pti_tsne_affinities_ws_floats(n)
+    if floats <= 0:
+        raise ValueError(f"tsne_affinities: unsupported shape {tuple(d2.shape)} (2 <= n <= 8192)")
+    out = _latent_out(out, (n, n), d2, "tsne_affinities")
+    if out.data_ptr() == d2.data_ptr():
+        raise ValueError("tsne_affinities: out must not be d2")
+    sums = torch.empty(2, dtype=torch.float64, device=d2.device)
+    stream = _stream()
+    ws = _scratch("tsne_aff", (n,), floats, d2.device, stream)
+    L.check(L.lib().pti_tsne_affinities(_ptr(d2), d2.stride(0), n, perplexity, _ptr(out), out.stride(0), _ptr(sums), _ptr(ws),
+                                        stream), "pti_tsne_affinities")
+    return out, sums
+
+
+def tsne_step(p, y_in, y_out, update, gains, record, *, sums, exaggeration, momentum, lr, with_record=True):
+    """One iteration of exact t-SNE's gradient descent (``pti_tsne_step``: sklearn's ``_kl_divergence`` gradient and
+    ``_gradient_descent`` update).  ``p`` fp32 [n, n] and ``sums`` from ``tsne_affinities``; ``y_in`` -> ``y_out`` (two
+    distinct contiguous fp32 [n, 2] buffers), ``update`` / ``gains`` fp32 [n, 2] in place; ``record``: fp64 [2] device
+    tensor that receives ``{KL(exaggeration * P || Q) at y_in, |gain * grad|_2}`` when ``with_record`` (an iteration
+    without a record skips the fp64 work behind the KL value).
+    Runs on the current stream, no host sync; bitwise reproducible."""
+    p = _tsne_matrix(p, "tsne_step: p")
+    n = p.shape[0]
+    for name, t in (("y_in", y_in), ("y_out", y_out), ("update", update), ("gains", gains)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"tsne_step: {name}: expected a CUDA(HIP) tensor")
+        _chk(t, F32, f"tsne_step: {name}", 2)
+        if t.shape[0] != n or t.device != p.device:
+            raise ValueError(f"tsne_step: {name} must be [{n}, 2] on {p.device}, got {tuple(t.shape)}")
+        if t.shape[1] != 2:
+            raise ValueError(f"tsne_step: {name} has {t.shape[1]} columns; only n_components = 2 is built")
+    for name, t in (("record", record), ("sums", sums)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"tsne_step: {name}: expected a CUDA(HIP) tensor")
+        _chk(t, torch.float64, f"tsne_step: {name}", 1)
+        if t.numel() != 2 or t.device != p.device:
+            raise ValueError(f"tsne_step: {name} must hold 2 doubles on {p.device}")
+    if y_in.data_ptr() == y_out.data_ptr():
+        raise ValueError("tsne_step: y_out must not be y_in")
+    floats = L.lib().pti_tsne_step_ws_floats(n, 2)
+    if floats <= 0:
+        raise ValueError(f"tsne_step: unsupported shape {tuple(p.shape)} (2 <= n <= 8192)")
+    stream = _stream()
+    ws = _scratch("tsne_step", (n,), floats, p.device, stream)
+    L.check(L.lib().pti_tsne_step(_ptr(p), p.stride(0), n, 2, _ptr(y_in), _ptr(y_out), _ptr(update), _ptr(gains), _ptr(sums),
+                                  float(exaggeration), float(momentum), float(lr), _ptr(record), int(bool(with_record)),
+                                  _ptr(ws), stream), "pti_tsne_step")
+
+
 # ---- mask geometry (csrc/mask_geometry.hip; include/pti_vae.h "mask geometry") -----------------------------------------
 MASK_DTYPES = (torch.uint8, torch.uint16, F32)   # dtype of the mask buffer for `elem` 0, 1, 2 of pti_mask_geometry
 MASK_ROW_CAP = 4096                                     # the kernel's bound on max_h
