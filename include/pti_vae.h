@@ -37,7 +37,9 @@ typedef void* pti_stream_t; /* hipStream_t */
                                Still 5: pti_mlp_head_fwd / pti_mlp_head_ws_floats / pti_regression_metrics, appended after
                                pti_mask_geometry in the same way.
                                Still 5: pti_conv_wgrad_batched_mode (a host-only query) appended in the same way.
-                               Still 5: pti_tsne_affinities / pti_tsne_step (+ their _ws_floats) appended in the same way. */
+                               Still 5: pti_tsne_affinities / pti_tsne_step (+ their _ws_floats) appended in the same way.
+                               Still 5: pti_umap_knn / pti_umap_graph (+ its _capacity, _ws_floats) / pti_umap_epoch appended
+                               in the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -607,6 +609,40 @@ int64_t pti_tsne_step_ws_floats(int n, int n_components);
 int pti_tsne_step(const float* p, int64_t ldp, int n, int n_components, const float* y_in, float* y_out, float* update,
                   float* gains, const double* plogp2, float exaggeration, float momentum, float lr, double* record,
                   int with_record, float* workspace, pti_stream_t s);
+
+/* ---- UMAP of the latent-space analysis (umap-learn: smooth_knn_dist, compute_membership_strengths, the fuzzy union with
+ *      set_op_mix_ratio = local_connectivity = bandwidth = 1, optimize_layout_euclidean; csrc/umap.hip) ----
+ * 3 <= n <= 8192 rows, 2 <= k <= 256 neighbours, k < n, TWO output columns, 1 <= n_epochs <= 2000.  No atomics; every sum has
+ * one order: results are bitwise reproducible.  Everything runs on the caller's stream without a host synchronisation.
+ * Refused before any launch: null pointers, n < 3, k outside [2, n), n_epochs < 1, a row stride below n, a capacity below
+ * pti_umap_graph_capacity, a misaligned workspace, a or b <= 0, epoch < 0, a negative_sample_rate outside [0, 64],
+ * y_out == y_in (PTI_EINVAL); n > 8192, k > 256, n_epochs > 2000, epoch >= 2000, n_components != 2 (PTI_EUNSUPPORTED).
+ * pti_umap_knn: dist = fp32 distances [n][n], row stride ldd in ELEMENTS.  knn_idx int32 / knn_dist fp32 [n][k]: the k
+ *   smallest entries of each row, ascending by (distance, column); the diagonal competes like any other entry.  Exact.
+ * pti_umap_graph: per row rho = the smallest non-zero distance among the k (0 if none); sigma from umap-learn's search in
+ *   fp64 on sum_{j=1..k-1} (d_j - rho > 0 ? exp(-(d_j - rho) / sigma) : 1) = log2 k (from 1, doubling while no upper bound
+ *   is known, bisecting after, at most 64 rounds, stop at 1e-5), floored at 1e-3 * the row's mean distance (rho > 0) or the
+ *   mean of all kNN distances (rho = 0); strengths 0 for the row itself, 1 for d - rho <= 0, exp(-(d - rho) / sigma)
+ *   otherwise; w = a + a^T - a o a^T (symmetric bit for bit); entries with w * n_epochs < wmax are dropped.  CSR output:
+ *   indptr int32 [n + 1] (indptr[n] = nnz, a DEVICE value), indices int32 (ascending within a row), weights fp32 and
+ *   rate int32 = floor(w * 2^20 / wmax), each of `capacity` >= pti_umap_graph_capacity(n, k) = min(2 n k, n^2) entries
+ *   of which the first nnz are written; rho, sigma fp32 [n].  workspace: pti_umap_graph_ws_floats(n, k) floats (a dense
+ *   [n][n] scratch and a little more), 8-byte aligned.  Both queries are pure host arithmetic; 0 = unsupported shape.
+ * pti_umap_epoch: one layout epoch as a Jacobi sweep, y_in -> y_out (fp32 [n][2], two distinct buffers).  The edge at CSR
+ *   position p fires iff ((epoch + 1) * rate[p] >> 20) > (epoch * rate[p] >> 20).  For vertex i, with d2 = |y_i - y_j|^2,
+ *     y_out[i] = y_in[i] + alpha * (2 sum_fired clip4(g_att (y_i - y_j)) + sum_fired sum_{s < rate} clip4(g_rep (y_i - y_v)))
+ *     g_att = -2 a b d2^(b-1) / (a d2^b + 1),   g_rep = 2 b / ((0.001 + d2) (a d2^b + 1)),   both 0 at d2 = 0,
+ *   clip4 clamps each coordinate to [-4, 4], v = (uint64(h) * n) >> 32 with
+ *   h = mix(mix(seed + epoch) ^ (p * negative_sample_rate + s)) and mix the lowbias32 of pti_elastic_field.  `capacity` is
+ *   the length of indices / rate: positions outside it and column indices outside [0, n) are skipped.                       */
+int pti_umap_knn(const float* dist, int64_t ldd, int n, int k, int* knn_idx, float* knn_dist, pti_stream_t s);
+int64_t pti_umap_graph_capacity(int n, int k);
+int64_t pti_umap_graph_ws_floats(int n, int k);
+int pti_umap_graph(const int* knn_idx, const float* knn_dist, int n, int k, int n_epochs, int* indptr, int* indices,
+                   float* weights, int* rate, int64_t capacity, float* rho, float* sigma, float* workspace, pti_stream_t s);
+int pti_umap_epoch(const int* indptr, const int* indices, const int* rate, int64_t capacity, int n, int n_components,
+                   const float* y_in, float* y_out, double a, double b, double alpha, int epoch, uint32_t seed,
+                   int negative_sample_rate, pti_stream_t s);
 
 #ifdef __cplusplus
 }

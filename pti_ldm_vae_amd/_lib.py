@@ -74,6 +74,8 @@ _P = C.c_void_p
 _I = C.c_int
 _I64 = C.c_int64
 _F = C.c_float
+_D = C.c_double
+_U32 = C.c_uint32
 
 # symbol -> (restype, argtypes); every symbol include/pti_vae.h declares is listed here and
 # tests/test_abi.py checks the two lists against each other.
@@ -169,6 +171,11 @@ SIGNATURES = {
     "pti_tsne_affinities": (_I, [_P, _I64, _I, _F, _P, _I64, _P, _P, _P]),
     "pti_tsne_step_ws_floats": (_I64, [_I, _I]),
     "pti_tsne_step": (_I, [_P, _I64, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _P, _I, _P, _P]),
+    "pti_umap_knn": (_I, [_P, _I64, _I, _I, _P, _P, _P]),
+    "pti_umap_graph_capacity": (_I64, [_I, _I]),
+    "pti_umap_graph_ws_floats": (_I64, [_I, _I]),
+    "pti_umap_graph": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "pti_umap_epoch": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P, _D, _D, _D, _I, _U32, _I, _P]),
 }
 
 _lib = None

@@ -4,9 +4,10 @@ error texts and output files).
 What differs is where the arithmetic runs.  The latents of all images stay on the device as one ``[N, D]`` matrix
 (D = 4 096 .. 40 960); the per-patient distance statistics of all patients come out of ONE ``ops.latent_group_stats``
 call, and PCA takes the centred Gram matrix ``Xc Xc^T`` from ``ops.latent_pairwise(mode="dot", center=mean)`` and
-diagonalises that N x N matrix in fp64 on the host.  Only results cross to the host.  UMAP and the default t-SNE are
+diagonalises that N x N matrix in fp64 on the host.  Only results cross to the host.  The default UMAP and t-SNE are
 host libraries fed with the PCA output; ``reduce_dimensionality_tsne(backend="hip")`` is exact t-SNE on the device
-(``ops.tsne_affinities`` / ``ops.tsne_step``, csrc/tsne.hip)."""
+(``ops.tsne_affinities`` / ``ops.tsne_step``, csrc/tsne.hip) and ``reduce_dimensionality_umap(backend="hip")`` UMAP on the
+device (``ops.umap_knn`` / ``ops.umap_graph`` / ``ops.umap_epoch``, csrc/umap.hip)."""
 from __future__ import annotations
 
 import os
@@ -38,6 +39,49 @@ def load_image_paths(data_dir: str, max_images: int | None = None, extensions: l
         found.extend(glob(os.path.join(data_dir, f"*{ext if ext.startswith('.') else '.' + ext}")))
     found.sort()
     return found if max_images is None else found[:max_images]
+
+
+def find_ab_params(spread: float = 1.0, min_dist: float = 0.5) -> tuple[float, float]:
+    """umap-learn's ``find_ab_params`` without scipy: the least-squares fit of ``1 / (1 + a x^(2b))`` to the curve that is 1
+    below ``min_dist`` and ``exp(-(x - min_dist) / spread)`` above it, on 300 points of [0, 3 spread] -> (a, b).  A damped
+    Gauss-Newton iteration from (1, 1), the start ``scipy.optimize.curve_fit`` uses."""
+    x = np.linspace(0.0, 3.0 * spread, 300)
+    target = np.where(x < min_dist, 1.0, np.exp(-(x - min_dist) / spread))
+    logx = np.log(np.where(x > 0, x, 1.0))
+
+    def residual(a, b):
+        return 1.0 / (1.0 + a * x ** (2.0 * b)) - target
+
+    a, b, damp = 1.0, 1.0, 1e-3
+    r = residual(a, b)
+    for _ in range(500):
+        xb = x ** (2.0 * b)
+        f2 = (1.0 / (1.0 + a * xb)) ** 2
+        jac = np.stack([-xb * f2, -2.0 * a * logx * xb * f2], axis=1)
+        grad, hess = jac.T @ r, jac.T @ jac
+        while True:
+            step = np.linalg.solve(hess + damp * np.diag(np.diag(hess)), -grad)
+            a2, b2 = a + step[0], b + step[1]
+            r2 = residual(a2, b2) if a2 > 0 and b2 > 0 else None
+            if r2 is not None and r2 @ r2 <= r @ r:
+                damp = max(damp / 10.0, 1e-15)
+                break
+            damp *= 10.0
+            if damp > 1e15:
+                return float(a), float(b)
+        a, b, r = a2, b2, r2
+        if np.abs(step).max() <= 1e-14 * max(a, b):
+            break
+    return float(a), float(b)
+
+
+class UmapResult:
+    """What ``reduce_dimensionality_umap(backend="hip")`` returns beside the embedding (there is no umap-learn model):
+    ``embedding_`` fp64 [N, 2] on the host, the curve parameters ``a_`` / ``b_``, ``n_epochs_`` and ``graph_``, the fuzzy
+    graph as the device CSR of ``ops.umap_graph``."""
+
+    def __init__(self, embedding, a, b, n_epochs, graph):
+        self.embedding_, self.a_, self.b_, self.n_epochs_, self.graph_ = embedding, a, b, n_epochs, graph
 
 
 def _is_device_tensor(x) -> bool:
@@ -224,12 +268,30 @@ class LatentSpaceAnalyzer:
         return n_samples
 
     def reduce_dimensionality_umap(self, latent_vectors, n_components: int = 2, n_neighbors: int = 40, min_dist: float = 0.5,
-                                   random_state: int = 42, pca_components: int = 50) -> tuple[np.ndarray, object]:
-        """PCA, then UMAP on the host -> (reduced ``[N, n_components]``, the fitted UMAP model)."""
+                                   random_state: int = 42, pca_components: int = 50, backend: str = "umap-learn",
+                                   n_epochs: int | None = None) -> tuple[np.ndarray, object]:
+        """PCA, then UMAP -> (reduced ``[N, n_components]``, the fitted UMAP model).
+
+        ``backend="umap-learn"``: the host library; ``n_epochs`` is not used.  ``backend="hip"``: UMAP on the device
+        (``ops.umap_knn`` / ``ops.umap_graph`` / ``ops.umap_epoch``), no host library; ``n_components`` must be 2,
+        3 <= N <= 8192, ``n_neighbors`` at most 256, ``n_epochs`` at most 2000 (None: 500, umap-learn's choice up to
+        10000 rows).  It starts from the first two principal components, each scaled to [0, 10]; ``random_state`` seeds
+        the negative sampling: the same seed gives the same bits.  Returns ``(Y fp64 [N, 2], UmapResult)``."""
+        if backend not in ("umap-learn", "hip"):
+            raise ValueError(f"backend must be 'umap-learn' or 'hip', got {backend!r}")
         n_samples = self._check_reduction_input(latent_vectors, pca_components)
         if n_neighbors >= n_samples:
             raise ValueError(f"n_neighbors ({n_neighbors}) must be < n_samples ({n_samples}). "
                              f"Reduce n_neighbors or provide more samples.")
+        if backend == "hip":
+            if n_components != 2:
+                raise ValueError(f"backend='hip' computes n_components=2 only, got {n_components}")
+            n_epochs = 500 if n_epochs is None else int(n_epochs)
+            if not 2 <= n_neighbors <= 256 or not 3 <= n_samples <= 8192 or not 1 <= n_epochs <= 2000:
+                raise ValueError(f"backend='hip' needs 2 <= n_neighbors <= 256, 3 <= n_samples <= 8192 and 1 <= n_epochs <= "
+                                 f"2000, got n_neighbors={n_neighbors}, n_samples={n_samples}, n_epochs={n_epochs}")
+            vectors_pca, _ = self.reduce_dimensionality_pca(latent_vectors, pca_components)
+            return self._umap_device(vectors_pca, n_neighbors, min_dist, n_epochs, random_state)
         try:
             import umap
         except ImportError as e:
@@ -237,6 +299,40 @@ class LatentSpaceAnalyzer:
         vectors_pca, _ = self.reduce_dimensionality_pca(latent_vectors, pca_components)
         model = umap.UMAP(n_components=n_components, random_state=random_state, n_neighbors=n_neighbors, min_dist=min_dist)
         return model.fit_transform(vectors_pca), model
+
+    @staticmethod
+    def umap_init(vectors_pca: np.ndarray) -> np.ndarray:
+        """The start of the device UMAP: the first two PCA columns, each min-max scaled to [0, 10] (umap-learn's rescaling
+        of any initialisation), rounded to fp32 -> ``[N, 2]`` fp32."""
+        y = np.zeros((len(vectors_pca), 2))
+        y[:, :min(2, vectors_pca.shape[1])] = vectors_pca[:, :2]
+        span = np.ptp(y, axis=0)
+        return (10.0 * (y - y.min(axis=0)) / np.where(span > 0, span, 1.0)).astype(np.float32)
+
+    @staticmethod
+    def umap_layout(graph, y0: torch.Tensor, a: float, b: float, n_epochs: int, seed: int, negative_sample_rate: int = 5,
+                    stop: int | None = None) -> torch.Tensor:
+        """Epochs 0 .. ``stop`` - 1 (all ``n_epochs`` by default) of the layout from ``y0`` -> Y fp32 [N, 2] on the device.
+        One launch per epoch on the current stream, ``alpha = 1 - e / n_epochs``, nothing comes back to the host."""
+        from .. import ops
+        y = [y0.to(torch.float32).contiguous().clone(), torch.empty(y0.shape[0], 2, dtype=torch.float32, device=y0.device)]
+        cur = 0
+        for e in range(n_epochs if stop is None else stop):
+            ops.umap_epoch(graph, y[cur], y[cur ^ 1], a=a, b=b, alpha=1.0 - e / n_epochs, epoch=e, seed=seed,
+                           negative_sample_rate=negative_sample_rate)
+            cur ^= 1
+        return y[cur]
+
+    def _umap_device(self, vectors_pca: np.ndarray, n_neighbors: int, min_dist: float, n_epochs: int,
+                     seed: int) -> tuple[np.ndarray, UmapResult]:
+        from .. import ops
+        a, b = find_ab_params(1.0, min_dist)
+        dist = ops.latent_pairwise(self._to_device_matrix(vectors_pca))
+        knn_idx, knn_dist = ops.umap_knn(dist, n_neighbors)
+        graph = ops.umap_graph(knn_idx, knn_dist, n_epochs)
+        y0 = torch.from_numpy(self.umap_init(vectors_pca)).to(dist.device)
+        y = self.umap_layout(graph, y0, a, b, n_epochs, int(seed) & 0xFFFFFFFF).cpu().double().numpy()
+        return y, UmapResult(y, a, b, n_epochs, graph)
 
     def reduce_dimensionality_tsne(self, latent_vectors, n_components: int = 2, perplexity: int = 30, random_state: int = 42,
                                    pca_components: int = 50, backend: str = "sklearn", max_iter: int = 1000,

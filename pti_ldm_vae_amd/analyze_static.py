@@ -4,8 +4,9 @@
     python -m pti_ldm_vae_amd.analyze_static --vae-weights W.pth --config-file CFG.json --folder-edente DIR [--folder-dente DIR]
 
 Same options and defaults, plus ``--method pca`` (the projection is the first two principal components; also the
-fallback, with a warning, when umap-learn / scikit-learn is not installed), ``--cache-dir``, ``--batch-size`` and
-``--tsne-backend hip`` (``--method tsne`` as exact t-SNE on the device: deterministic, no host library).
+fallback, with a warning, when umap-learn / scikit-learn is not installed), ``--cache-dir``, ``--batch-size``,
+``--tsne-backend hip`` (``--method tsne`` as exact t-SNE on the device: deterministic, no host library) and
+``--umap-backend hip`` (``--method umap`` on the device: deterministic for a ``--seed``, no host library).
 Outputs in ``--output-dir``: ``<method>_projection.png`` (matplotlib; ``.html`` through plotly when that fails),
 ``color_legend.txt`` with ``--color-by-patient``, and with two groups ``distance_metrics.txt``,
 ``exams_sorted_by_distance.txt`` and ``latents.npz`` (latents, ids, paths and projection of each group).
@@ -24,10 +25,11 @@ from .analysis import LatentCache, LatentSpaceAnalyzer, load_image_paths
 
 
 class _Args(argparse.Namespace):
-    """The namespace ``parse_args`` fills.  ``--tsne-backend`` lives here as a class default and enters the instance only
-    when it is given, so a command line without it parses to exactly the attributes it always had."""
+    """The namespace ``parse_args`` fills.  ``--tsne-backend`` and ``--umap-backend`` live here as class defaults and enter
+    the instance only when they are given, so a command line without them parses to exactly the attributes it always had."""
 
     tsne_backend = "sklearn"
+    umap_backend = "umap-learn"
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -48,6 +50,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     parser.add_argument("--tsne-backend", type=str, choices=["sklearn", "hip"], default=argparse.SUPPRESS,
                         help="t-SNE implementation: sklearn (host, Barnes-Hut; default) or hip (exact, on the device, "
                              "deterministic, needs no host library)")
+    parser.add_argument("--umap-backend", type=str, choices=["umap-learn", "hip"], default=argparse.SUPPRESS,
+                        help="UMAP implementation: umap-learn (host; default) or hip (on the device, deterministic for a "
+                             "--seed, needs no host library)")
     parser.add_argument("--seed", type=int, default=42, help="Random seed for reproducibility")
     parser.add_argument("--subtitle", type=str, default=None, help="Optional subtitle for the plot")
     parser.add_argument("--dpi", type=int, default=300, help="DPI for output PNG (default: 300)")
@@ -98,7 +103,8 @@ def project(analyzer: LatentSpaceAnalyzer, latents: np.ndarray, args: argparse.N
         try:
             if args.method == "umap":
                 return analyzer.reduce_dimensionality_umap(latents, n_neighbors=args.n_neighbors, min_dist=args.min_dist,
-                                                           random_state=args.seed, pca_components=min(n, 50))[0], "umap"
+                                                           random_state=args.seed, pca_components=min(n, 50),
+                                                           backend=getattr(args, "umap_backend", "umap-learn"))[0], "umap"
             backend = getattr(args, "tsne_backend", "sklearn")       # a namespace built by hand may not carry it
             if backend == "sklearn":
                 print("(This may take a few minutes...)")

@@ -30,13 +30,7 @@ constexpr int FT_W = 64, FT_H = 16, FT_THREADS = 256;
 constexpr int FIELD_MAX_RADIUS = PTI_ELASTIC_MAX_RADIUS;
 constexpr int FIELD_MAX_TAPS = ((2 * FIELD_MAX_RADIUS + 1 + 3) / 4) * 4;   // 64
 
-// lowbias32 (Chris Wellons, "Prospecting for hash functions", public domain): a 32-bit bijection with good avalanche
-__device__ __forceinline__ uint32_t aug_mix(uint32_t h) {
-  h ^= h >> 16; h *= 0x7feb352du;
-  h ^= h >> 15; h *= 0x846ca68bu;
-  h ^= h >> 16;
-  return h;
-}
+__device__ __forceinline__ uint32_t aug_mix(uint32_t h) { return lowbias32(h); }   // pti_common.h
 // uniform in [-1, 1): the top 24 bits of the hash as a signed fraction -- exact in fp32
 __device__ __forceinline__ float aug_noise(uint32_t k0, uint32_t k1c, uint32_t i) {
   const uint32_t h = aug_mix(aug_mix(i + k0) ^ k1c);

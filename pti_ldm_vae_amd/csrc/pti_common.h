@@ -210,6 +210,15 @@ __device__ __forceinline__ f32x2 gn_silu2(f32x2 x, f32x2 sc, f32x2 sh) {
   return v * r;
 }
 
+// lowbias32 (Chris Wellons, "Prospecting for hash functions", public domain): a 32-bit bijection with good avalanche;
+// the counter-based generator of the augmentation noise and of UMAP's negative samples
+__device__ __forceinline__ uint32_t lowbias32(uint32_t h) {
+  h ^= h >> 16; h *= 0x7feb352du;
+  h ^= h >> 15; h *= 0x846ca68bu;
+  h ^= h >> 16;
+  return h;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 import torch
 
@@ -969,6 +970,89 @@ def tsne_step(p, y_in, y_out, update, gains, record, *, sums, exaggeration, mome
     L.check(L.lib().pti_tsne_step(_ptr(p), p.stride(0), n, 2, _ptr(y_in), _ptr(y_out), _ptr(update), _ptr(gains), _ptr(sums),
                                   float(exaggeration), float(momentum), float(lr), _ptr(record), int(bool(with_record)),
                                   _ptr(ws), stream), "pti_tsne_step")
+
+
+# ---- UMAP (csrc/umap.hip; include/pti_vae.h "UMAP of the latent-space analysis") -----------------------------------------
+UmapGraph = namedtuple("UmapGraph", "indptr indices weights rate rho sigma nnz")
+UmapGraph.__doc__ = """The fuzzy graph of ``umap_graph`` as device CSR: ``indptr`` int32 [n + 1]; ``indices`` int32 (ascending
+within a row), ``weights`` fp32 and ``rate`` int32, allocated for min(2 n k, n^2) entries of which the first ``nnz`` are
+written; ``rho`` / ``sigma`` fp32 [n]; ``nnz`` = ``indptr[n]``, a 0-d DEVICE tensor (reading it is a host sync)."""
+I32 = torch.int32
+
+
+def umap_knn(dist, k, *, out=None):
+    """The ``k`` nearest neighbours of every row of the fp32 distance matrix ``dist`` [n, n] (``pti_umap_knn``) ->
+    ``(knn_idx int32 [n, k], knn_dist fp32 [n, k])``, ascending by (distance, column): the diagonal competes like any other
+    entry and equal distances go by the lower column.  Exact.  ``out``: a pair of tensors to write into.
+    3 <= n <= 8192, 2 <= k <= 256, k < n.  Runs on the current stream, no host sync."""
+    dist = _tsne_matrix(dist, "umap_knn: dist")
+    n, k = dist.shape[0], int(k)
+    if not (3 <= n <= 8192 and 2 <= k <= 256 and k < n):
+        raise ValueError(f"umap_knn: unsupported shape {tuple(dist.shape)} with k={k} (3 <= n <= 8192, 2 <= k <= 256, k < n)")
+    idx, kd = (None, None) if out is None else out
+    idx = _out(idx, (n, k), I32, dist.device, "umap_knn: knn_idx")
+    kd = _out(kd, (n, k), F32, dist.device, "umap_knn: knn_dist")
+    L.check(L.lib().pti_umap_knn(_ptr(dist), dist.stride(0), n, k, _ptr(idx), _ptr(kd), _stream()), "pti_umap_knn")
+    return idx, kd
+
+
+def umap_graph(knn_idx, knn_dist, n_epochs):
+    """UMAP's fuzzy graph from the neighbours of ``umap_knn`` (``pti_umap_graph``: umap-learn's ``smooth_knn_dist`` with the
+    search in fp64, ``compute_membership_strengths``, the union ``w = a + a^T - a o a^T``, entries below
+    ``wmax / n_epochs`` dropped) -> ``UmapGraph``.  ``rate = floor(w 2^20 / wmax)`` is the integer form of umap-learn's
+    ``epochs_per_sample``.  The CSR arrays are allocated for the upper bound min(2 n k, n^2), so nothing comes back to the
+    host.  1 <= n_epochs <= 2000.  Runs on the current stream, no host sync; bitwise reproducible."""
+    for name, t, dtype in (("knn_idx", knn_idx, I32), ("knn_dist", knn_dist, F32)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"umap_graph: {name}: expected a CUDA(HIP) tensor")
+        _chk(t, dtype, f"umap_graph: {name}", 2)
+    n, k = knn_idx.shape
+    if tuple(knn_dist.shape) != (n, k) or knn_dist.device != knn_idx.device:
+        raise ValueError(f"umap_graph: knn_dist must be [{n}, {k}] on {knn_idx.device}, got {tuple(knn_dist.shape)}")
+    n_epochs = int(n_epochs)
+    floats, cap = L.lib().pti_umap_graph_ws_floats(n, k), L.lib().pti_umap_graph_capacity(n, k)
+    if floats <= 0 or not 1 <= n_epochs <= 2000:
+        raise ValueError(f"umap_graph: unsupported shape {tuple(knn_idx.shape)} with n_epochs={n_epochs} "
+                         f"(3 <= n <= 8192, 2 <= k <= 256, k < n, 1 <= n_epochs <= 2000)")
+    dev = knn_idx.device
+    indptr = torch.empty(n + 1, dtype=I32, device=dev)
+    indices, rate = torch.empty(cap, dtype=I32, device=dev), torch.empty(cap, dtype=I32, device=dev)
+    weights = torch.empty(cap, dtype=F32, device=dev)
+    rho, sigma = torch.empty(n, dtype=F32, device=dev), torch.empty(n, dtype=F32, device=dev)
+    stream = _stream()
+    ws = _scratch("umap_graph", (n, k), floats, dev, stream)
+    L.check(L.lib().pti_umap_graph(_ptr(knn_idx), _ptr(knn_dist), n, k, n_epochs, _ptr(indptr), _ptr(indices), _ptr(weights),
+                                   _ptr(rate), cap, _ptr(rho), _ptr(sigma), _ptr(ws), stream), "pti_umap_graph")
+    return UmapGraph(indptr, indices, weights, rate, rho, sigma, indptr[n])
+
+
+def umap_epoch(graph, y_in, y_out, *, a, b, alpha, epoch, seed, negative_sample_rate=5):
+    """One layout epoch of UMAP as a Jacobi sweep (``pti_umap_epoch``): ``y_in`` -> ``y_out``, two distinct contiguous fp32
+    [n, 2] buffers.  ``graph``: an ``UmapGraph`` (only ``indptr``, ``indices`` and ``rate`` are read).  An edge fires in the
+    epochs its ``rate`` selects; a fired edge attracts its vertex (twice: the mirrored edge fires in the same epoch) and
+    repels it from ``negative_sample_rate`` vertices drawn by a hash of (``seed``, ``epoch``, CSR position).
+    Runs on the current stream, no host sync; bitwise reproducible."""
+    for name, t, dtype in (("indptr", graph.indptr, I32), ("indices", graph.indices, I32), ("rate", graph.rate, I32),
+                           ("y_in", y_in, F32), ("y_out", y_out, F32)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"umap_epoch: {name}: expected a CUDA(HIP) tensor")
+        _chk(t, dtype, f"umap_epoch: {name}", 2 if name[0] == "y" else 1)
+    n = graph.indptr.numel() - 1
+    if not 3 <= n <= 8192:
+        raise ValueError(f"umap_epoch: unsupported shape: {n} rows (3 <= n <= 8192)")
+    cap = graph.indices.numel()
+    if graph.rate.numel() != cap or cap > n * n:
+        raise ValueError(f"umap_epoch: indices ({cap}) and rate ({graph.rate.numel()}) must have one length of at most n^2")
+    for name, t in (("y_in", y_in), ("y_out", y_out)):
+        if t.shape[0] != n or t.device != graph.indptr.device:
+            raise ValueError(f"umap_epoch: {name} must be [{n}, 2] on {graph.indptr.device}, got {tuple(t.shape)}")
+        if t.shape[1] != 2:
+            raise ValueError(f"umap_epoch: {name} has {t.shape[1]} columns; only n_components = 2 is built")
+    if y_in.data_ptr() == y_out.data_ptr():
+        raise ValueError("umap_epoch: y_out must not be y_in")
+    L.check(L.lib().pti_umap_epoch(_ptr(graph.indptr), _ptr(graph.indices), _ptr(graph.rate), cap, n, 2, _ptr(y_in), _ptr(y_out),
+                                   float(a), float(b), float(alpha), int(epoch), int(seed) & 0xFFFFFFFF,
+                                   int(negative_sample_rate), _stream()), "pti_umap_epoch")
 
 
 # ---- mask geometry (csrc/mask_geometry.hip; include/pti_vae.h "mask geometry") -----------------------------------------
