@@ -39,7 +39,9 @@ typedef void* pti_stream_t; /* hipStream_t */
                                Still 5: pti_conv_wgrad_batched_mode (a host-only query) appended in the same way.
                                Still 5: pti_tsne_affinities / pti_tsne_step (+ their _ws_floats) appended in the same way.
                                Still 5: pti_umap_knn / pti_umap_graph (+ its _capacity, _ws_floats) / pti_umap_epoch appended
-                               in the same way. */
+                               in the same way.
+                               Still 5: pti_umap_knn_cross / pti_umap_transform_graph (+ its _ws_floats) /
+                               pti_umap_transform_layout appended in the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -643,6 +645,38 @@ int pti_umap_graph(const int* knn_idx, const float* knn_dist, int n, int k, int 
 int pti_umap_epoch(const int* indptr, const int* indices, const int* rate, int64_t capacity, int n, int n_components,
                    const float* y_in, float* y_out, double a, double b, double alpha, int epoch, uint32_t seed,
                    int negative_sample_rate, pti_stream_t s);
+
+/* ---- UMAP transform: new rows into a fitted embedding (umap-learn's UMAP.transform; csrc/umap.hip) ----
+ * m new rows against n training rows: 1 <= m <= 8192, 3 <= n <= 8192, 2 <= k <= 256, k < n, 1 <= n_epochs <= 2000, two
+ * output columns.  No atomics, every sum has one order: bitwise reproducible.  Caller's stream, no host synchronisation.
+ * Refused before any launch: null pointers, m < 1, n < 3, k outside [2, n), n_epochs < 1, a row stride below n, a
+ * misaligned workspace, an epoch range outside 0 <= begin <= end <= n_epochs, a or b or initial_alpha <= 0, a
+ * negative_sample_rate outside [0, 64], y_out overlapping y_train, y_out overlapping y_in without being y_in
+ * (PTI_EINVAL); m or n > 8192, k > 256, n_epochs > 2000 (PTI_EUNSUPPORTED).
+ * pti_umap_knn_cross: pti_umap_knn for a rectangular dist = fp32 [m][n] (new rows x training rows), row stride ldd in
+ *   ELEMENTS -> knn_idx int32 / knn_dist fp32 [m][k], ascending by (distance, column).  Exact.
+ * pti_umap_transform_graph: rho = 0 for every row (local_connectivity - 1 = 0); sigma from pti_umap_graph's fp64 search on
+ *   sum_{t=1..k-1} (d_t > 0 ? exp(-d_t / sigma) : 1) = log2 k, floored at 1e-3 * the fp64 mean of all m k distances;
+ *   weights[i][t] = d <= 0 ? 1 : exp(-d / sigma) as fp32 (bipartite: no self exclusion); wmax = the largest of them;
+ *   rate[i][t] = floor(w * 2^20 / wmax) where w * n_epochs >= wmax, else 0; y0[i] = sum_t w_it Y[idx_it] / sum_t w_it
+ *   over ALL k slots (umap-learn normalises before it thresholds; an index outside [0, n) takes no part), summed in
+ *   fp64.  sigma fp32 [m], weights fp32 / rate int32 [m][k], y0 fp32 [m][2].  workspace:
+ *   pti_umap_transform_graph_ws_floats(m, n, k) floats, 8-byte aligned (host arithmetic; 0 = unsupported shape).
+ * pti_umap_transform_layout: epochs epoch_begin .. epoch_end - 1 of n_epochs in ONE launch, one wavefront per new row.
+ *   Per epoch e, alpha = initial_alpha * (1 - e / n_epochs); slot t of row i fires iff rate > 0 and
+ *   ((e + 1) * rate >> 20) > (e * rate >> 20); with p = i * k + t,
+ *     y[i] = fp32(y[i] + alpha * sum_fired (clip4(g_att (y_i - Y[idx])) + sum_{s < negative_sample_rate} clip4(g_rep (y_i - Y[v]))))
+ *   with g_att, g_rep, the hash and the d2 > 0 rule of pti_umap_epoch and v = (mix(mix(seed + e) ^ (p * negative_sample_rate
+ *   + s)) * n) >> 32.  The attraction is NOT doubled: the training end does not move and there is no mirrored edge.  The
+ *   rounding to fp32 after every epoch makes [0, T) in one launch bit-identical to T launches of one epoch.  A slot whose
+ *   index lies outside [0, n) never fires.  y_in == y_out is allowed (a row reads only itself and y_train).            */
+int pti_umap_knn_cross(const float* dist, int64_t ldd, int m, int n, int k, int* knn_idx, float* knn_dist, pti_stream_t s);
+int64_t pti_umap_transform_graph_ws_floats(int m, int n, int k);
+int pti_umap_transform_graph(const int* knn_idx, const float* knn_dist, int m, int k, const float* y_train, int n, int n_epochs,
+                             float* sigma, float* weights, int* rate, float* y0, float* workspace, pti_stream_t s);
+int pti_umap_transform_layout(const int* knn_idx, const int* rate, int m, int k, const float* y_train, int n, const float* y_in,
+                              float* y_out, double a, double b, double initial_alpha, int n_epochs, int epoch_begin,
+                              int epoch_end, uint32_t seed, int negative_sample_rate, pti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -176,6 +176,10 @@ SIGNATURES = {
     "pti_umap_graph_ws_floats": (_I64, [_I, _I]),
     "pti_umap_graph": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "pti_umap_epoch": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P, _D, _D, _D, _I, _U32, _I, _P]),
+    "pti_umap_knn_cross": (_I, [_P, _I64, _I, _I, _I, _P, _P, _P]),
+    "pti_umap_transform_graph_ws_floats": (_I64, [_I, _I, _I]),
+    "pti_umap_transform_graph": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "pti_umap_transform_layout": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _D, _D, _D, _I, _I, _I, _U32, _I, _P]),
 }
 
 _lib = None

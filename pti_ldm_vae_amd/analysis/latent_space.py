@@ -7,7 +7,9 @@ call, and PCA takes the centred Gram matrix ``Xc Xc^T`` from ``ops.latent_pairwi
 diagonalises that N x N matrix in fp64 on the host.  Only results cross to the host.  The default UMAP and t-SNE are
 host libraries fed with the PCA output; ``reduce_dimensionality_tsne(backend="hip")`` is exact t-SNE on the device
 (``ops.tsne_affinities`` / ``ops.tsne_step``, csrc/tsne.hip) and ``reduce_dimensionality_umap(backend="hip")`` UMAP on the
-device (``ops.umap_knn`` / ``ops.umap_graph`` / ``ops.umap_epoch``, csrc/umap.hip)."""
+device (``ops.umap_knn`` / ``ops.umap_graph`` / ``ops.umap_epoch``, csrc/umap.hip); its ``UmapResult.transform`` places new rows
+into the fitted embedding (``PcaModel.transform``, ``ops.umap_knn_cross`` / ``ops.umap_transform_graph`` /
+``ops.umap_transform_layout``)."""
 from __future__ import annotations
 
 import os
@@ -75,13 +77,81 @@ def find_ab_params(spread: float = 1.0, min_dist: float = 0.5) -> tuple[float, f
     return float(a), float(b)
 
 
+class PcaModel:
+    """What ``LatentSpaceAnalyzer.fit_pca`` returns: ``embedding_`` fp64 [N, c] (the projections of the training rows, what
+    ``reduce_dimensionality_pca`` returns), ``explained_variance_ratio_`` [c], ``mean_`` fp64 [D], and ``transform`` for new
+    rows.  The model keeps its own fp32 copy of the training rows on the device (134 MB at 8192 x 4096), so a later change
+    of the caller's latents does not reach it: a new row is projected through its centred dot products with them, the
+    principal axes are never formed."""
+
+    def __init__(self, rows: torch.Tensor, mean: torch.Tensor, embedding, ratio, u_signed, lam) -> None:
+        self._rows, self._mean = rows, mean
+        self.embedding_, self.explained_variance_ratio_ = embedding, ratio
+        self.mean_ = mean.cpu().double().numpy()
+        n, d = rows.shape
+        keep = lam > max(n, d) * np.finfo(np.float64).eps * (lam.max() if lam.size else 0.0)
+        self._axes = np.where(keep, u_signed / np.sqrt(np.where(keep, lam, 1.0)), 0.0)       # [N, c]: U signs / sqrt(lambda)
+
+    def transform(self, new_rows) -> np.ndarray:
+        """-> fp64 [m, c].  The centred cross Gram matrix ``Xnew_c Xc^T`` comes from the device
+        (``ops.latent_pairwise(mode="dot", center=mean)``); times ``U signs / sqrt(lambda)`` in fp64 on the host, which is
+        ``Xnew_c V``.  A column whose ``lambda`` is not above ``max(N, D) eps lambda_max`` comes out as zero."""
+        from .. import ops
+        if new_rows.ndim != 2 or new_rows.shape[1] != self._rows.shape[1]:
+            raise ValueError(f"Expected [m, {self._rows.shape[1]}] rows (the columns of the fit), got {tuple(new_rows.shape)}")
+        if isinstance(new_rows, torch.Tensor):
+            x = new_rows.to(self._rows.device, torch.float32)
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(new_rows, dtype=np.float32)).to(self._rows.device)
+        cross = ops.latent_pairwise(x, self._rows, mode="dot", center=self._mean).cpu().double().numpy()
+        return cross @ self._axes
+
+
 class UmapResult:
     """What ``reduce_dimensionality_umap(backend="hip")`` returns beside the embedding (there is no umap-learn model):
     ``embedding_`` fp64 [N, 2] on the host, the curve parameters ``a_`` / ``b_``, ``n_epochs_`` and ``graph_``, the fuzzy
-    graph as the device CSR of ``ops.umap_graph``."""
+    graph as the device CSR of ``ops.umap_graph``.  With the keyword-only state ``reduce_dimensionality_umap`` adds (the
+    ``PcaModel``, the PCA'd training rows and the fp32 embedding on the device, ``n_neighbors``, the seed, whether
+    ``n_epochs`` was defaulted) it can ``transform`` new rows."""
 
-    def __init__(self, embedding, a, b, n_epochs, graph):
+    def __init__(self, embedding, a, b, n_epochs, graph, *, pca=None, train_pca=None, train_embedding=None,
+                 n_neighbors=None, seed=None, n_epochs_defaulted=None):
         self.embedding_, self.a_, self.b_, self.n_epochs_, self.graph_ = embedding, a, b, n_epochs, graph
+        self._pca, self._train_pca, self._train_embedding = pca, train_pca, train_embedding
+        self._n_neighbors, self._seed, self._n_epochs_defaulted = n_neighbors, seed, n_epochs_defaulted
+
+    def transform(self, new_latents, n_epochs: int | None = None, random_state: int | None = None) -> np.ndarray:
+        """New rows ``[m, D]`` into the fitted embedding -> fp64 [m, 2]; the fit does not change (umap-learn's
+        ``UMAP.transform``).  The rows go through the fit's PCA, find their ``n_neighbors`` nearest training rows there
+        (exactly), get umap-learn's transform graph and start at the weighted mean of their neighbours' points; then
+        ``n_epochs`` epochs against the frozen embedding in one launch.  ``n_epochs=None``: 100 when the fit's was
+        defaulted (umap-learn's rule up to 10000 rows), else ``max(1, fit n_epochs // 3)``; 1 <= n_epochs <= 2000.
+        ``random_state=None``: the fit's seed.  At most 8192 new rows, not chunked: the sigma floor and the largest weight
+        are taken over all of them.  The same arguments give the same bits."""
+        from .. import ops
+        if self._pca is None or self._train_pca is None or self._train_embedding is None:
+            raise RuntimeError("this UmapResult carries no fitted state to transform with: only the result of "
+                               "reduce_dimensionality_umap(backend='hip') does")
+        if new_latents.ndim != 2:
+            raise ValueError(f"Expected 2D array, got {new_latents.ndim}D array")
+        m = len(new_latents)
+        if not 1 <= m <= 8192:
+            raise ValueError(f"transform places 1 to 8192 new rows at once, got {m} (chunks would not reproduce the whole: "
+                             f"the sigma floor and the largest weight are taken over all new rows)")
+        if n_epochs is None:
+            n_epochs = 100 if self._n_epochs_defaulted else max(1, self.n_epochs_ // 3)
+        n_epochs = int(n_epochs)
+        if not 1 <= n_epochs <= 2000:
+            raise ValueError(f"transform needs 1 <= n_epochs <= 2000, got {n_epochs}")
+        seed = self._seed if random_state is None else random_state
+        new_pca = self._pca.transform(new_latents)
+        dev = self._train_pca.device
+        dist = ops.latent_pairwise(torch.from_numpy(np.ascontiguousarray(new_pca, dtype=np.float32)).to(dev), self._train_pca)
+        knn_idx, knn_dist = ops.umap_knn_cross(dist, self._n_neighbors)
+        tg = ops.umap_transform_graph(knn_idx, knn_dist, self._train_embedding, n_epochs)
+        ops.umap_transform_layout(tg, self._train_embedding, tg.y0, tg.y0, a=self.a_, b=self.b_, n_epochs=n_epochs,
+                                  seed=int(seed) & 0xFFFFFFFF)
+        return tg.y0.cpu().double().numpy()
 
 
 def _is_device_tensor(x) -> bool:
@@ -240,6 +310,12 @@ class LatentSpaceAnalyzer:
         matrix ``G = Xc Xc^T`` are computed on the device; ``G = U diag(lambda) U^T`` in fp64 on the host, and the
         projections are ``U sqrt(lambda)`` -- what ``PCA(svd_solver="full").fit_transform`` returns.  Signs: the entry of
         largest magnitude of each column of U is positive (sklearn's ``svd_flip``, u-based)."""
+        model = self.fit_pca(latent_vectors, n_components)
+        return model.embedding_, model.explained_variance_ratio_
+
+    def fit_pca(self, latent_vectors, n_components: int = 50) -> PcaModel:
+        """``reduce_dimensionality_pca`` that keeps what it fitted -> ``PcaModel``: ``embedding_`` and
+        ``explained_variance_ratio_`` are that function's two results, ``transform`` projects new rows."""
         from .. import ops
         if latent_vectors.ndim != 2:
             raise ValueError(f"Expected 2D array, got {latent_vectors.ndim}D array")
@@ -247,7 +323,10 @@ class LatentSpaceAnalyzer:
         if not 1 <= n_components <= min(n, d):
             raise ValueError(f"n_components={n_components} must be between 1 and min(n_samples, n_features)={min(n, d)}")
         x = self._to_device_matrix(latent_vectors)
-        gram = ops.latent_pairwise(x, mode="dot", center=x.mean(dim=0)).cpu().double().numpy()
+        if x is latent_vectors:                                # the caller's own device tensor: the model keeps a copy of its own
+            x = x.clone()
+        mean = x.mean(dim=0)
+        gram = ops.latent_pairwise(x, mode="dot", center=mean).cpu().double().numpy()
         lam, u = np.linalg.eigh(gram)
         lam, u = np.clip(lam[::-1], 0.0, None), u[:, ::-1]
         total = float(np.trace(gram))
@@ -255,7 +334,7 @@ class LatentSpaceAnalyzer:
         top = np.argmax(np.abs(u), axis=0)
         signs = np.sign(u[top, np.arange(n_components)])
         signs[signs == 0] = 1.0
-        return u * signs * np.sqrt(lam), (lam / total if total > 0 else np.zeros_like(lam))
+        return PcaModel(x, mean, u * signs * np.sqrt(lam), (lam / total if total > 0 else np.zeros_like(lam)), u * signs, lam)
 
     @staticmethod
     def _check_reduction_input(latent_vectors, pca_components: int) -> int:
@@ -286,12 +365,12 @@ class LatentSpaceAnalyzer:
         if backend == "hip":
             if n_components != 2:
                 raise ValueError(f"backend='hip' computes n_components=2 only, got {n_components}")
-            n_epochs = 500 if n_epochs is None else int(n_epochs)
+            defaulted, n_epochs = n_epochs is None, 500 if n_epochs is None else int(n_epochs)
             if not 2 <= n_neighbors <= 256 or not 3 <= n_samples <= 8192 or not 1 <= n_epochs <= 2000:
                 raise ValueError(f"backend='hip' needs 2 <= n_neighbors <= 256, 3 <= n_samples <= 8192 and 1 <= n_epochs <= "
                                  f"2000, got n_neighbors={n_neighbors}, n_samples={n_samples}, n_epochs={n_epochs}")
-            vectors_pca, _ = self.reduce_dimensionality_pca(latent_vectors, pca_components)
-            return self._umap_device(vectors_pca, n_neighbors, min_dist, n_epochs, random_state)
+            pca = self.fit_pca(latent_vectors, pca_components)
+            return self._umap_device(pca.embedding_, n_neighbors, min_dist, n_epochs, random_state, pca, defaulted)
         try:
             import umap
         except ImportError as e:
@@ -323,16 +402,19 @@ class LatentSpaceAnalyzer:
             cur ^= 1
         return y[cur]
 
-    def _umap_device(self, vectors_pca: np.ndarray, n_neighbors: int, min_dist: float, n_epochs: int,
-                     seed: int) -> tuple[np.ndarray, UmapResult]:
+    def _umap_device(self, vectors_pca: np.ndarray, n_neighbors: int, min_dist: float, n_epochs: int, seed: int,
+                     pca: PcaModel | None = None, n_epochs_defaulted: bool = False) -> tuple[np.ndarray, UmapResult]:
         from .. import ops
         a, b = find_ab_params(1.0, min_dist)
-        dist = ops.latent_pairwise(self._to_device_matrix(vectors_pca))
+        train_pca = self._to_device_matrix(vectors_pca)
+        dist = ops.latent_pairwise(train_pca)
         knn_idx, knn_dist = ops.umap_knn(dist, n_neighbors)
         graph = ops.umap_graph(knn_idx, knn_dist, n_epochs)
         y0 = torch.from_numpy(self.umap_init(vectors_pca)).to(dist.device)
-        y = self.umap_layout(graph, y0, a, b, n_epochs, int(seed) & 0xFFFFFFFF).cpu().double().numpy()
-        return y, UmapResult(y, a, b, n_epochs, graph)
+        y_dev = self.umap_layout(graph, y0, a, b, n_epochs, int(seed) & 0xFFFFFFFF)
+        y = y_dev.cpu().double().numpy()
+        return y, UmapResult(y, a, b, n_epochs, graph, pca=pca, train_pca=train_pca, train_embedding=y_dev,
+                             n_neighbors=n_neighbors, seed=seed, n_epochs_defaulted=n_epochs_defaulted)
 
     def reduce_dimensionality_tsne(self, latent_vectors, n_components: int = 2, perplexity: int = 30, random_state: int = 42,
                                    pca_components: int = 50, backend: str = "sklearn", max_iter: int = 1000,

@@ -6,7 +6,9 @@
 Same options and defaults, plus ``--method pca`` (the projection is the first two principal components; also the
 fallback, with a warning, when umap-learn / scikit-learn is not installed), ``--cache-dir``, ``--batch-size``,
 ``--tsne-backend hip`` (``--method tsne`` as exact t-SNE on the device: deterministic, no host library) and
-``--umap-backend hip`` (``--method umap`` on the device: deterministic for a ``--seed``, no host library).
+``--umap-backend hip`` (``--method umap`` on the device: deterministic for a ``--seed``, no host library) and
+``--umap-fit-group edente`` (with ``--umap-backend hip`` and two groups: UMAP is fitted on the edentulous group alone and
+the dentulous group is placed into that embedding, as the reference does; the default ``all`` fits on both).
 Outputs in ``--output-dir``: ``<method>_projection.png`` (matplotlib; ``.html`` through plotly when that fails),
 ``color_legend.txt`` with ``--color-by-patient``, and with two groups ``distance_metrics.txt``,
 ``exams_sorted_by_distance.txt`` and ``latents.npz`` (latents, ids, paths and projection of each group).
@@ -25,11 +27,13 @@ from .analysis import LatentCache, LatentSpaceAnalyzer, load_image_paths
 
 
 class _Args(argparse.Namespace):
-    """The namespace ``parse_args`` fills.  ``--tsne-backend`` and ``--umap-backend`` live here as class defaults and enter
-    the instance only when they are given, so a command line without them parses to exactly the attributes it always had."""
+    """The namespace ``parse_args`` fills.  ``--tsne-backend``, ``--umap-backend`` and ``--umap-fit-group`` live here as class
+    defaults and enter the instance only when they are given, so a command line without them parses to exactly the
+    attributes it always had."""
 
     tsne_backend = "sklearn"
     umap_backend = "umap-learn"
+    umap_fit_group = "all"
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -53,6 +57,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     parser.add_argument("--umap-backend", type=str, choices=["umap-learn", "hip"], default=argparse.SUPPRESS,
                         help="UMAP implementation: umap-learn (host; default) or hip (on the device, deterministic for a "
                              "--seed, needs no host library)")
+    parser.add_argument("--umap-fit-group", type=str, choices=["all", "edente"], default=argparse.SUPPRESS,
+                        help="Rows UMAP is fitted on: all (both groups together; default) or edente (the edentulous group "
+                             "alone, the dentulous group is then placed into its embedding; needs --umap-backend hip)")
     parser.add_argument("--seed", type=int, default=42, help="Random seed for reproducibility")
     parser.add_argument("--subtitle", type=str, default=None, help="Optional subtitle for the plot")
     parser.add_argument("--dpi", type=int, default=300, help="DPI for output PNG (default: 300)")
@@ -119,6 +126,15 @@ def project(analyzer: LatentSpaceAnalyzer, latents: np.ndarray, args: argparse.N
     return proj, "pca"
 
 
+def project_fit_first(analyzer: LatentSpaceAnalyzer, first: np.ndarray, second: np.ndarray,
+                      args: argparse.Namespace) -> tuple[list[np.ndarray], str]:
+    """``--umap-fit-group edente``: the device UMAP fitted on ``first`` alone, ``second`` placed into that embedding by
+    ``UmapResult.transform`` -> ([projection of first, projection of second], "umap")."""
+    fitted, model = analyzer.reduce_dimensionality_umap(first, n_neighbors=args.n_neighbors, min_dist=args.min_dist,
+                                                        random_state=args.seed, pca_components=min(len(first), 50), backend="hip")
+    return [fitted, model.transform(second)], "umap"
+
+
 def save_projection_plot(groups: list, output_path: Path, title: str, subtitle: str | None, dpi: int,
                          patient_to_color: dict | None) -> Path:
     """``groups``: ``(points [n, 2], ids, name)``; edente = open circles, dente = filled.  -> the file written: the PNG
@@ -164,6 +180,10 @@ def main(argv=None) -> None:
     from .utils.cli_common import init_device_and_seed, load_config_and_model
     _lib.refuse_wrong_result_env("analyze_static.py")
     args = parse_args(argv)
+    fit_first = args.method == "umap" and getattr(args, "umap_fit_group", "all") == "edente" and bool(args.folder_dente)
+    if fit_first and getattr(args, "umap_backend", "umap-learn") != "hip":
+        raise SystemExit("analyze_static: --umap-fit-group edente places the second group with the device UMAP's transform; "
+                         "add --umap-backend hip")
     device = init_device_and_seed(args.seed)
     np.random.seed(args.seed)
     output_dir = Path(args.output_dir)
@@ -184,10 +204,13 @@ def main(argv=None) -> None:
             groups.append((latents, ids, paths, name))
 
     print(f"Computing {args.method.upper()} projection...")
-    combined = np.concatenate([g[0] for g in groups]) if len(groups) > 1 else groups[0][0]
-    projection, method = project(analyzer, combined, args)
-    split = len(groups[0][0])
-    projected = [projection[:split]] + ([projection[split:]] if len(groups) > 1 else [])
+    if fit_first:
+        projected, method = project_fit_first(analyzer, groups[0][0], groups[1][0], args)
+    else:
+        combined = np.concatenate([g[0] for g in groups]) if len(groups) > 1 else groups[0][0]
+        projection, method = project(analyzer, combined, args)
+        split = len(groups[0][0])
+        projected = [projection[:split]] + ([projection[split:]] if len(groups) > 1 else [])
 
     title = {"umap": "UMAP", "tsne": "t-SNE", "pca": "PCA"}[method]
     if len(groups) > 1:

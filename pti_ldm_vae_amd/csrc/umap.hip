@@ -31,6 +31,11 @@
 //     negative_sample_rate repulsions from vertices drawn by lowbias32(lowbias32(seed + e) ^ (p * rate + s)).  The
 //     coefficients, the clipped moves and their sums are fp64 (exp / log in fp64: an fp32 power under fast-math costs
 //     more digits than the whole rest of the epoch); lanes are folded by xor shuffles; y_out = fp32(y_in + alpha * sum).
+//   The transform (new rows into a fitted embedding): pti_umap_knn_cross is the kNN kernel over the [m][n]
+//     distances from new rows to training rows; pti_umap_transform_graph is umap-learn's transform preamble on the regular
+//     [m][k] slab (rho = 0, the same fp64 search, bipartite strengths, rates, the weighted-mean start point) in five small
+//     launches; pti_umap_transform_layout runs ALL epochs in one launch, one wavefront per new row, against the frozen
+//     training embedding.
 // No floating-point atomics, no atomics at all; every sum has one order: results are bitwise reproducible.
 #include <math.h>
 
@@ -143,27 +148,10 @@ __global__ __launch_bounds__(UM_THREADS) void umap_mean_kernel(const double* __r
   if (threadIdx.x == 0) mean[0] = s / ((double)n * (double)k);
 }
 
-__global__ __launch_bounds__(UM_THREADS) void umap_sigma_kernel(const int* __restrict__ knn_idx,
-                                                                const float* __restrict__ knn_dist, int n, int k,
-                                                                const double* __restrict__ rowsum,
-                                                                const double* __restrict__ mean, float* __restrict__ rho_out,
-                                                                float* __restrict__ sigma_out, float* __restrict__ dense) {
-  const int lane = threadIdx.x & 63, i = blockIdx.x * (UM_THREADS / 64) + (threadIdx.x >> 6);
-  if (i >= n) return;                                    // wave-uniform
-  float d[UM_MAX_K / 64];
-  float least = INFINITY;
-#pragma unroll
-  for (int c = 0; c < UM_MAX_K / 64; ++c) {
-    const int t = lane + 64 * c;
-    d[c] = t < k ? knn_dist[(long long)i * k + t] : 0.f;
-    if (d[c] > 0.f) least = fminf(least, d[c]);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) least = fminf(least, __shfl_xor(least, o, 64));
-  const float rho = least == INFINITY ? 0.f : least;
-  double dd[UM_MAX_K / 64];
-#pragma unroll
-  for (int c = 0; c < UM_MAX_K / 64; ++c) dd[c] = (double)d[c] - (double)rho;
+// umap-learn's search for sigma on one wavefront: sum_{t=1..k-1} (dd_t > 0 ? exp(-dd_t / sigma) : 1) = log2 k, from 1,
+// doubling while no upper bound is known, bisecting after, at most 64 rounds, stop at 1e-5.  dd[c] belongs to slot
+// lane + 64 c; the sum is lane-strided and folded by xor shuffles, so every lane returns the same bits.
+__device__ __forceinline__ double um_sigma_search(const double* dd, int lane, int k) {
   const double target = log2((double)k);
   double lo = 0.0, hi = 0.0, mid = 1.0;
   bool has_hi = false;
@@ -185,6 +173,31 @@ __global__ __launch_bounds__(UM_THREADS) void umap_sigma_kernel(const int* __res
       mid = has_hi ? (lo + hi) * 0.5 : mid * 2.0;
     }
   }
+  return mid;
+}
+
+__global__ __launch_bounds__(UM_THREADS) void umap_sigma_kernel(const int* __restrict__ knn_idx,
+                                                                const float* __restrict__ knn_dist, int n, int k,
+                                                                const double* __restrict__ rowsum,
+                                                                const double* __restrict__ mean, float* __restrict__ rho_out,
+                                                                float* __restrict__ sigma_out, float* __restrict__ dense) {
+  const int lane = threadIdx.x & 63, i = blockIdx.x * (UM_THREADS / 64) + (threadIdx.x >> 6);
+  if (i >= n) return;                                    // wave-uniform
+  float d[UM_MAX_K / 64];
+  float least = INFINITY;
+#pragma unroll
+  for (int c = 0; c < UM_MAX_K / 64; ++c) {
+    const int t = lane + 64 * c;
+    d[c] = t < k ? knn_dist[(long long)i * k + t] : 0.f;
+    if (d[c] > 0.f) least = fminf(least, d[c]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) least = fminf(least, __shfl_xor(least, o, 64));
+  const float rho = least == INFINITY ? 0.f : least;
+  double dd[UM_MAX_K / 64];
+#pragma unroll
+  for (int c = 0; c < UM_MAX_K / 64; ++c) dd[c] = (double)d[c] - (double)rho;
+  const double mid = um_sigma_search(dd, lane, k);
   const double floor_at = 1e-3 * (rho > 0.f ? rowsum[i] / (double)k : mean[0]);
   const double sigma = fmax(mid, floor_at);
   if (lane == 0) {
@@ -390,6 +403,133 @@ __global__ __launch_bounds__(UM_THREADS) void umap_epoch_kernel(UmEpoch u) {
   }
 }
 
+// ---- transform: new rows into a fitted embedding ----------------------------------------------------------------------
+// One wavefront per new row.  rho = 0 for every row (umap-learn's transform runs with local_connectivity - 1 = 0), so the
+// search sees the distances themselves and the floor is 1e-3 * the mean of all m k distances; the strengths are
+// bipartite: a zero distance is 1, the row itself is not excluded.  The start point is the strength-weighted mean of the
+// neighbours' training points over all k slots, summed in fp64 (lane-strided, xor fold).
+__global__ __launch_bounds__(UM_THREADS) void umap_tsigma_kernel(const int* __restrict__ knn_idx,
+                                                                 const float* __restrict__ knn_dist, int m, int k,
+                                                                 const float* __restrict__ y_train, int n,
+                                                                 const double* __restrict__ mean, float* __restrict__ sigma_out,
+                                                                 float* __restrict__ weights, float* __restrict__ rowmax,
+                                                                 float* __restrict__ y0) {
+  const int lane = threadIdx.x & 63, i = blockIdx.x * (UM_THREADS / 64) + (threadIdx.x >> 6);
+  if (i >= m) return;                                    // wave-uniform
+  double dd[UM_MAX_K / 64];
+#pragma unroll
+  for (int c = 0; c < UM_MAX_K / 64; ++c) {
+    const int t = lane + 64 * c;
+    dd[c] = t < k ? (double)knn_dist[(long long)i * k + t] : 0.0;
+  }
+  const double sigma = fmax(um_sigma_search(dd, lane, k), 1e-3 * mean[0]);
+  float top = 0.f;
+  double sw = 0.0, sx = 0.0, sy = 0.0;
+#pragma unroll
+  for (int c = 0; c < UM_MAX_K / 64; ++c) {
+    const int t = lane + 64 * c;
+    if (t >= k) continue;
+    const float v = dd[c] > 0.0 ? (float)exp(-dd[c] / sigma) : 1.f;
+    weights[(long long)i * k + t] = v;
+    top = fmaxf(top, v);
+    const int j = knn_idx[(long long)i * k + t];
+    if ((unsigned)j >= (unsigned)n) continue;            // not a training row: no part in the start point
+    sw += (double)v;
+    sx += (double)v * (double)y_train[2 * j];
+    sy += (double)v * (double)y_train[2 * j + 1];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) top = fmaxf(top, __shfl_xor(top, o, 64));
+  sw = um_wave_sum(sw);
+  sx = um_wave_sum(sx);
+  sy = um_wave_sum(sy);
+  if (lane == 0) {
+    sigma_out[i] = (float)sigma;
+    rowmax[i] = top;
+    y0[2 * i] = sw > 0.0 ? (float)(sx / sw) : 0.f;
+    y0[2 * i + 1] = sw > 0.0 ? (float)(sy / sw) : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(UM_THREADS) void umap_trate_kernel(const float* __restrict__ weights, int count, int n_epochs,
+                                                                const float* __restrict__ wmax, int* __restrict__ rate) {
+  const int p = blockIdx.x * UM_THREADS + threadIdx.x;
+  if (p >= count) return;
+  const float v = weights[p], top = wmax[0];
+  rate[p] = um_kept(v, top, n_epochs) ? um_rate(v, top) : 0;
+}
+
+struct UmTransform {
+  const int* knn_idx;
+  const int* rate;
+  const float* y_train;
+  const float* y_in;
+  float* y_out;
+  double a, b, initial_alpha;
+  int m, k, n, n_epochs, epoch_begin, epoch_end, negatives;
+  uint32_t seed;
+};
+
+// One wavefront per new row, all epochs in one launch: the row reads the frozen training embedding and itself only.  Its
+// index and rate slots (at most four per lane) and its point live in registers; the point is rounded to fp32 at the end
+// of every epoch, so epochs [0, T) in one launch are T launches of one epoch each, bit for bit.  The training embedding
+// (at most 64 KB, read-only) is read through the caches.
+__global__ __launch_bounds__(UM_THREADS) void umap_transform_kernel(UmTransform u) {
+  const int lane = threadIdx.x & 63, i = blockIdx.x * (UM_THREADS / 64) + (threadIdx.x >> 6);
+  if (i >= u.m) return;                                  // wave-uniform
+  int idx[UM_MAX_K / 64];
+  unsigned long long rate[UM_MAX_K / 64];
+#pragma unroll
+  for (int c = 0; c < UM_MAX_K / 64; ++c) {
+    const int t = lane + 64 * c;
+    idx[c] = t < u.k ? u.knn_idx[(long long)i * u.k + t] : -1;
+    const int r = t < u.k ? u.rate[(long long)i * u.k + t] : 0;
+    rate[c] = (unsigned)idx[c] < (unsigned)u.n && r > 0 ? (unsigned long long)r : 0ull;   // outside [0, n): never fires
+  }
+  float yx = u.y_in[2 * i], yy = u.y_in[2 * i + 1];
+  for (int epoch = u.epoch_begin; epoch < u.epoch_end; ++epoch) {
+    const unsigned long long e = (unsigned long long)epoch;
+    const uint32_t base = lowbias32(u.seed + (uint32_t)epoch);
+    const double px = (double)yx, py = (double)yy;
+    double sx = 0.0, sy = 0.0;
+#pragma unroll
+    for (int c = 0; c < UM_MAX_K / 64; ++c) {
+      if ((((e + 1) * rate[c]) >> 20) <= ((e * rate[c]) >> 20)) continue;
+      {
+        const double dx = px - (double)u.y_train[2 * idx[c]], dy = py - (double)u.y_train[2 * idx[c] + 1];
+        const double d2 = dx * dx + dy * dy;
+        if (d2 > 0.0) {
+          const double pw = exp(u.b * log(d2));
+          const double g = -2.0 * u.a * u.b * (pw / d2) / (u.a * pw + 1.0);
+          sx += um_clip(g * dx);
+          sy += um_clip(g * dy);
+        }
+      }
+      const uint32_t p = (uint32_t)(i * u.k + lane + 64 * c);
+      for (int s = 0; s < u.negatives; ++s) {
+        const uint32_t h = lowbias32(base ^ (p * (uint32_t)u.negatives + (uint32_t)s));
+        const int v = (int)(((unsigned long long)h * (unsigned long long)u.n) >> 32);
+        const double dx = px - (double)u.y_train[2 * v], dy = py - (double)u.y_train[2 * v + 1];
+        const double d2 = dx * dx + dy * dy;
+        if (d2 > 0.0) {
+          const double g = 2.0 * u.b / ((0.001 + d2) * (u.a * exp(u.b * log(d2)) + 1.0));
+          sx += um_clip(g * dx);
+          sy += um_clip(g * dy);
+        }
+      }
+    }
+    sx = um_wave_sum(sx);                                // the same bits in every lane
+    sy = um_wave_sum(sy);
+    const double alpha = u.initial_alpha * (1.0 - (double)epoch / (double)u.n_epochs);
+    yx = (float)(px + alpha * sx);
+    yy = (float)(py + alpha * sy);
+  }
+  if (lane == 0) {
+    u.y_out[2 * i] = yx;
+    u.y_out[2 * i + 1] = yy;
+  }
+}
+
 int um_pow2_at_least(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -411,20 +551,43 @@ int um_check_shape(const char* who, int n, int k) {
   return PTI_OK;
 }
 
+// the checks of the transform's entry points: m new rows against n training rows; 0 when the shape is fine
+int um_check_cross(const char* who, int m, int n, int k) {
+  if (m < 1) PTI_FAIL(PTI_EINVAL, "%s: bad dimension m=%d (at least 1 new row)", who, m);
+  if (n < UM_MIN_N) PTI_FAIL(PTI_EINVAL, "%s: bad dimension n=%d (at least %d training rows)", who, n, UM_MIN_N);
+  if (k < 2 || k >= n) PTI_FAIL(PTI_EINVAL, "%s: bad dimension k=%d (2 <= k < n=%d)", who, k, n);
+  if (m > UM_MAX_N || n > UM_MAX_N || k > UM_MAX_K)
+    PTI_FAIL(PTI_EUNSUPPORTED, "%s: unsupported shape m=%d n=%d k=%d (at most %d rows, %d neighbours)", who, m, n, k, UM_MAX_N,
+             UM_MAX_K);
+  return PTI_OK;
+}
+int um_check_epochs(const char* who, int n_epochs) {
+  if (n_epochs < 1) PTI_FAIL(PTI_EINVAL, "%s: bad dimension n_epochs=%d (at least 1)", who, n_epochs);
+  if (n_epochs > UM_MAX_EPOCHS) PTI_FAIL(PTI_EUNSUPPORTED, "%s: unsupported n_epochs=%d (at most %d)", who, n_epochs, UM_MAX_EPOCHS);
+  return PTI_OK;
+}
+bool um_cross_ok(int m, int n, int k) { return m >= 1 && m <= UM_MAX_N && um_shape_ok(n, k); }
+
+// one workgroup per row of dist [rows][n]; the checks are the callers'
+int um_launch_knn(const char* who, const float* dist, int64_t ldd, int rows, int n, int k, int* knn_idx, float* knn_dist,
+                  pti_stream_t s) {
+  const int m = um_pow2_at_least(k);
+  int lm = 0;
+  while ((1 << lm) < m) ++lm;
+  const int np2 = um_pow2_at_least(n > m ? n : m);       // at most 8192 keys: 64 KB of LDS
+  PTI_LAUNCH(umap_knn_kernel, dim3(rows), dim3(UM_THREADS), (size_t)np2 * sizeof(um_key), (hipStream_t)s, dist, (long long)ldd,
+             n, k, lm, np2, knn_idx, knn_dist);
+  PTI_CHECK_LAUNCH(who);
+  return PTI_OK;
+}
+
 }  // namespace
 
 extern "C" int pti_umap_knn(const float* dist, int64_t ldd, int n, int k, int* knn_idx, float* knn_dist, pti_stream_t s) {
   if (!dist || !knn_idx || !knn_dist) PTI_FAIL(PTI_EINVAL, "umap_knn: null pointer");
   if (int rc = um_check_shape("umap_knn", n, k)) return rc;
   if (ldd < n) PTI_FAIL(PTI_EINVAL, "umap_knn: row stride below the row length (ldd=%lld n=%d)", (long long)ldd, n);
-  const int m = um_pow2_at_least(k);
-  int lm = 0;
-  while ((1 << lm) < m) ++lm;
-  const int np2 = um_pow2_at_least(n > m ? n : m);       // at most 8192 keys: 64 KB of LDS
-  PTI_LAUNCH(umap_knn_kernel, dim3(n), dim3(UM_THREADS), (size_t)np2 * sizeof(um_key), (hipStream_t)s, dist, (long long)ldd, n,
-             k, lm, np2, knn_idx, knn_dist);
-  PTI_CHECK_LAUNCH("umap_knn");
-  return PTI_OK;
+  return um_launch_knn("umap_knn", dist, ldd, n, n, k, knn_idx, knn_dist, s);
 }
 
 extern "C" int64_t pti_umap_graph_capacity(int n, int k) { return um_shape_ok(n, k) ? um_capacity(n, k) : 0; }
@@ -513,5 +676,86 @@ extern "C" int pti_umap_epoch(const int* indptr, const int* indices, const int* 
   u.base = h;
   PTI_LAUNCH(umap_epoch_kernel, dim3(cdiv(n, UM_THREADS / 64)), dim3(UM_THREADS), 0, (hipStream_t)s, u);
   PTI_CHECK_LAUNCH("umap_epoch");
+  return PTI_OK;
+}
+
+// ---- transform ------------------------------------------------------------------------------------------------------------
+extern "C" int pti_umap_knn_cross(const float* dist, int64_t ldd, int m, int n, int k, int* knn_idx, float* knn_dist,
+                                  pti_stream_t s) {
+  if (!dist || !knn_idx || !knn_dist) PTI_FAIL(PTI_EINVAL, "umap_knn_cross: null pointer");
+  if (int rc = um_check_cross("umap_knn_cross", m, n, k)) return rc;
+  if (ldd < n) PTI_FAIL(PTI_EINVAL, "umap_knn_cross: row stride below the row length (ldd=%lld n=%d)", (long long)ldd, n);
+  return um_launch_knn("umap_knn_cross", dist, ldd, m, n, k, knn_idx, knn_dist, s);
+}
+
+extern "C" int64_t pti_umap_transform_graph_ws_floats(int m, int n, int k) {
+  return um_cross_ok(m, n, k) ? 2LL * (m + 1) + m + 1 : 0;
+}
+
+extern "C" int pti_umap_transform_graph(const int* knn_idx, const float* knn_dist, int m, int k, const float* y_train, int n,
+                                        int n_epochs, float* sigma, float* weights, int* rate, float* y0, float* workspace,
+                                        pti_stream_t s) {
+  if (!knn_idx || !knn_dist || !y_train || !sigma || !weights || !rate || !y0 || !workspace)
+    PTI_FAIL(PTI_EINVAL, "umap_transform_graph: null pointer");
+  if (int rc = um_check_cross("umap_transform_graph", m, n, k)) return rc;
+  if (int rc = um_check_epochs("umap_transform_graph", n_epochs)) return rc;
+  if (((uintptr_t)workspace & 7) != 0) PTI_FAIL(PTI_EINVAL, "umap_transform_graph: workspace must be 8-byte aligned");
+  const int waves = cdiv(m, UM_THREADS / 64);
+  double* rowsum = (double*)workspace;
+  double* mean = rowsum + m;
+  float* rowmax = (float*)(mean + 1);
+  float* wmax = rowmax + m;
+  hipStream_t st = (hipStream_t)s;
+  PTI_LAUNCH(umap_rowsum_kernel, dim3(waves), dim3(UM_THREADS), 0, st, knn_dist, m, k, rowsum);
+  PTI_CHECK_LAUNCH("umap_rowsum");
+  PTI_LAUNCH(umap_mean_kernel, dim3(1), dim3(UM_THREADS), 0, st, (const double*)rowsum, m, k, mean);
+  PTI_CHECK_LAUNCH("umap_mean");
+  PTI_LAUNCH(umap_tsigma_kernel, dim3(waves), dim3(UM_THREADS), 0, st, knn_idx, knn_dist, m, k, y_train, n, (const double*)mean,
+             sigma, weights, rowmax, y0);
+  PTI_CHECK_LAUNCH("umap_tsigma");
+  PTI_LAUNCH(umap_wmax_kernel, dim3(1), dim3(UM_THREADS), 0, st, (const float*)rowmax, m, wmax);
+  PTI_CHECK_LAUNCH("umap_wmax");
+  PTI_LAUNCH(umap_trate_kernel, dim3(cdiv(m * k, UM_THREADS)), dim3(UM_THREADS), 0, st, (const float*)weights, m * k, n_epochs,
+             (const float*)wmax, rate);
+  PTI_CHECK_LAUNCH("umap_trate");
+  return PTI_OK;
+}
+
+extern "C" int pti_umap_transform_layout(const int* knn_idx, const int* rate, int m, int k, const float* y_train, int n,
+                                         const float* y_in, float* y_out, double a, double b, double initial_alpha, int n_epochs,
+                                         int epoch_begin, int epoch_end, uint32_t seed, int negative_sample_rate, pti_stream_t s) {
+  if (!knn_idx || !rate || !y_train || !y_in || !y_out) PTI_FAIL(PTI_EINVAL, "umap_transform_layout: null pointer");
+  if (int rc = um_check_cross("umap_transform_layout", m, n, k)) return rc;
+  if (int rc = um_check_epochs("umap_transform_layout", n_epochs)) return rc;
+  if (epoch_begin < 0 || epoch_end < epoch_begin || epoch_end > n_epochs)
+    PTI_FAIL(PTI_EINVAL, "umap_transform_layout: bad epoch range [%d, %d) of %d", epoch_begin, epoch_end, n_epochs);
+  if (negative_sample_rate < 0 || negative_sample_rate > UM_MAX_NEG)
+    PTI_FAIL(PTI_EINVAL, "umap_transform_layout: negative_sample_rate %d outside [0, %d]", negative_sample_rate, UM_MAX_NEG);
+  if (!(a > 0.0) || !(b > 0.0)) PTI_FAIL(PTI_EINVAL, "umap_transform_layout: a=%g and b=%g must be positive", a, b);
+  if (!(initial_alpha > 0.0) || !(initial_alpha <= 1e6))
+    PTI_FAIL(PTI_EINVAL, "umap_transform_layout: initial_alpha=%g must be positive and finite", initial_alpha);
+  if (y_train < y_out + 2LL * m && y_out < y_train + 2LL * n)
+    PTI_FAIL(PTI_EINVAL, "umap_transform_layout: y_out must not overlap y_train (the training embedding is read by every row)");
+  if (y_in != y_out && y_in < y_out + 2LL * m && y_out < y_in + 2LL * m)
+    PTI_FAIL(PTI_EINVAL, "umap_transform_layout: y_out must be y_in itself or apart from it");
+  UmTransform u;
+  u.knn_idx = knn_idx;
+  u.rate = rate;
+  u.y_train = y_train;
+  u.y_in = y_in;
+  u.y_out = y_out;
+  u.a = a;
+  u.b = b;
+  u.initial_alpha = initial_alpha;
+  u.m = m;
+  u.k = k;
+  u.n = n;
+  u.n_epochs = n_epochs;
+  u.epoch_begin = epoch_begin;
+  u.epoch_end = epoch_end;
+  u.negatives = negative_sample_rate;
+  u.seed = seed;
+  PTI_LAUNCH(umap_transform_kernel, dim3(cdiv(m, UM_THREADS / 64)), dim3(UM_THREADS), 0, (hipStream_t)s, u);
+  PTI_CHECK_LAUNCH("umap_transform_layout");
   return PTI_OK;
 }

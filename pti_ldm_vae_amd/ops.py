@@ -1055,6 +1055,119 @@ def umap_epoch(graph, y_in, y_out, *, a, b, alpha, epoch, seed, negative_sample_
                                    int(negative_sample_rate), _stream()), "pti_umap_epoch")
 
 
+# ---- UMAP transform: new rows into a fitted embedding (csrc/umap.hip; include/pti_vae.h "UMAP transform") ------------------
+UmapTransformGraph = namedtuple("UmapTransformGraph", "indices weights rate sigma y0")
+UmapTransformGraph.__doc__ = """What ``umap_transform_graph`` makes of m new rows' k nearest training rows, a regular device slab:
+``indices`` int32 [m, k] (the ``knn_idx`` it was given), ``weights`` fp32 [m, k], ``rate`` int32 [m, k] (0 = dropped),
+``sigma`` fp32 [m] and the start points ``y0`` fp32 [m, 2]."""
+
+
+def _umap_cross_shape(who, m, n, k):
+    if not (1 <= m <= 8192 and 3 <= n <= 8192 and 2 <= k <= 256 and k < n):
+        raise ValueError(f"{who}: unsupported shape: {m} new rows, {n} training rows, k={k} "
+                         f"(1 <= m <= 8192, 3 <= n <= 8192, 2 <= k <= 256, k < n)")
+
+
+def _umap_embedding(who, name, t, rows, device):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
+    _chk(t, F32, f"{who}: {name}", 2)
+    if (rows is not None and t.shape[0] != rows) or t.device != device:
+        raise ValueError(f"{who}: {name} must be [{'n' if rows is None else rows}, 2] on {device}, got {tuple(t.shape)}")
+    if t.shape[1] != 2:
+        raise ValueError(f"{who}: {name} has {t.shape[1]} columns; only n_components = 2 is built")
+
+
+def umap_knn_cross(dist, k, *, out=None):
+    """The ``k`` nearest TRAINING rows of every new row (``pti_umap_knn_cross``): ``dist`` fp32 [m, n] holds the distances
+    from m new rows to n training rows -> ``(knn_idx int32 [m, k], knn_dist fp32 [m, k])``, ascending by (distance,
+    column); equal distances go by the lower column.  Exact.  A view with a row stride is read in place.  ``out``: a pair
+    of tensors to write into.  1 <= m <= 8192, 3 <= n <= 8192, 2 <= k <= 256, k < n.  Runs on the current stream, no host
+    sync."""
+    if not isinstance(dist, torch.Tensor) or not dist.is_cuda:
+        raise ValueError("umap_knn_cross: dist: expected a CUDA(HIP) tensor")
+    if dist.dtype != F32:
+        raise TypeError(f"umap_knn_cross: dist: expected fp32, got {dist.dtype}")
+    if dist.dim() != 2 or dist.stride(1) != 1 or dist.stride(0) < dist.shape[1]:
+        raise ValueError(f"umap_knn_cross: dist: expected an [m, n] matrix with dense rows, got {tuple(dist.shape)}")
+    (m, n), k = dist.shape, int(k)
+    _umap_cross_shape("umap_knn_cross", m, n, k)
+    idx, kd = (None, None) if out is None else out
+    idx = _out(idx, (m, k), I32, dist.device, "umap_knn_cross: knn_idx")
+    kd = _out(kd, (m, k), F32, dist.device, "umap_knn_cross: knn_dist")
+    L.check(L.lib().pti_umap_knn_cross(_ptr(dist), dist.stride(0), m, n, k, _ptr(idx), _ptr(kd), _stream()), "pti_umap_knn_cross")
+    return idx, kd
+
+
+def umap_transform_graph(knn_idx, knn_dist, y_train, n_epochs):
+    """umap-learn's ``transform`` preamble from the neighbours of ``umap_knn_cross`` (``pti_umap_transform_graph``) ->
+    ``UmapTransformGraph``.  ``rho = 0`` for every row; ``sigma`` from ``umap_graph``'s fp64 search, floored at 1e-3 times
+    the mean of all distances; bipartite strengths ``d <= 0 ? 1 : exp(-d / sigma)``; slots below ``wmax / n_epochs`` get
+    ``rate`` 0, the others ``floor(w 2^20 / wmax)``; ``y0`` = the strength-weighted mean of the neighbours' points in the
+    fitted embedding ``y_train`` fp32 [n, 2], over all k slots.  1 <= n_epochs <= 2000.  Runs on the current stream, no
+    host sync; bitwise reproducible."""
+    who = "umap_transform_graph"
+    for name, t, dtype in (("knn_idx", knn_idx, I32), ("knn_dist", knn_dist, F32)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
+        _chk(t, dtype, f"{who}: {name}", 2)
+    m, k = knn_idx.shape
+    dev = knn_idx.device
+    if tuple(knn_dist.shape) != (m, k) or knn_dist.device != dev:
+        raise ValueError(f"{who}: knn_dist must be [{m}, {k}] on {dev}, got {tuple(knn_dist.shape)}")
+    _umap_embedding(who, "y_train", y_train, None, dev)
+    n, n_epochs = y_train.shape[0], int(n_epochs)
+    _umap_cross_shape(who, m, n, k)
+    if not 1 <= n_epochs <= 2000:
+        raise ValueError(f"{who}: unsupported n_epochs={n_epochs} (1 <= n_epochs <= 2000)")
+    sigma, y0 = torch.empty(m, dtype=F32, device=dev), torch.empty(m, 2, dtype=F32, device=dev)
+    weights, rate = torch.empty(m, k, dtype=F32, device=dev), torch.empty(m, k, dtype=I32, device=dev)
+    stream = _stream()
+    ws = _scratch("umap_tgraph", (m, k), L.lib().pti_umap_transform_graph_ws_floats(m, n, k), dev, stream)
+    L.check(L.lib().pti_umap_transform_graph(_ptr(knn_idx), _ptr(knn_dist), m, k, _ptr(y_train), n, n_epochs, _ptr(sigma),
+                                             _ptr(weights), _ptr(rate), _ptr(y0), _ptr(ws), stream), "pti_umap_transform_graph")
+    return UmapTransformGraph(knn_idx, weights, rate, sigma, y0)
+
+
+def umap_transform_layout(tg, y_train, y_in, y_out, *, a, b, n_epochs, seed, start=0, stop=None, initial_alpha=0.25,
+                          negative_sample_rate=5):
+    """Epochs ``start`` .. ``stop`` - 1 (all ``n_epochs`` by default) of the layout of NEW rows against the fitted embedding
+    ``y_train`` fp32 [n, 2], in ONE launch (``pti_umap_transform_layout``): ``y_in`` -> ``y_out``, contiguous fp32 [m, 2];
+    ``y_out`` may be ``y_in`` (a row reads only itself and ``y_train``) but must not overlap ``y_train``.  ``tg``: an
+    ``UmapTransformGraph`` (only ``indices`` and ``rate`` are read).  ``alpha = initial_alpha (1 - e / n_epochs)``; a fired
+    slot attracts its row to the neighbour's training point (once: that end does not move) and repels it from
+    ``negative_sample_rate`` training points drawn by a hash of (``seed``, epoch, slot).  The point is rounded to fp32 after
+    every epoch, so any split of the epochs into launches gives the same bits.
+    Runs on the current stream, no host sync; bitwise reproducible."""
+    who = "umap_transform_layout"
+    for name, t in (("indices", tg.indices), ("rate", tg.rate)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
+        _chk(t, I32, f"{who}: {name}", 2)
+    m, k = tg.indices.shape
+    dev = tg.indices.device
+    if tuple(tg.rate.shape) != (m, k) or tg.rate.device != dev:
+        raise ValueError(f"{who}: rate must be [{m}, {k}] on {dev}, got {tuple(tg.rate.shape)}")
+    _umap_embedding(who, "y_train", y_train, None, dev)
+    _umap_embedding(who, "y_in", y_in, m, dev)
+    _umap_embedding(who, "y_out", y_out, m, dev)
+    n, n_epochs = y_train.shape[0], int(n_epochs)
+    _umap_cross_shape(who, m, n, k)
+    stop = n_epochs if stop is None else int(stop)
+    if not 1 <= n_epochs <= 2000 or not 0 <= int(start) <= stop <= n_epochs:
+        raise ValueError(f"{who}: unsupported n_epochs={n_epochs} with epochs [{start}, {stop}) "
+                         f"(1 <= n_epochs <= 2000, 0 <= start <= stop <= n_epochs)")
+    lo, hi = y_out.data_ptr(), y_out.data_ptr() + 8 * m
+    if y_train.data_ptr() < hi and lo < y_train.data_ptr() + 8 * n:
+        raise ValueError(f"{who}: y_out must not overlap y_train")
+    if y_in.data_ptr() != lo and y_in.data_ptr() < hi and lo < y_in.data_ptr() + 8 * m:
+        raise ValueError(f"{who}: y_out must be y_in itself or apart from it")
+    L.check(L.lib().pti_umap_transform_layout(_ptr(tg.indices), _ptr(tg.rate), m, k, _ptr(y_train), n, _ptr(y_in), _ptr(y_out),
+                                              float(a), float(b), float(initial_alpha), n_epochs, int(start), stop,
+                                              int(seed) & 0xFFFFFFFF, int(negative_sample_rate), _stream()),
+            "pti_umap_transform_layout")
+
+
 # ---- mask geometry (csrc/mask_geometry.hip; include/pti_vae.h "mask geometry") -----------------------------------------
 MASK_DTYPES = (torch.uint8, torch.uint16, F32)   # dtype of the mask buffer for `elem` 0, 1, 2 of pti_mask_geometry
 MASK_ROW_CAP = 4096                                     # the kernel's bound on max_h
