@@ -41,7 +41,8 @@ typedef void* pti_stream_t; /* hipStream_t */
                                Still 5: pti_umap_knn / pti_umap_graph (+ its _capacity, _ws_floats) / pti_umap_epoch appended
                                in the same way.
                                Still 5: pti_umap_knn_cross / pti_umap_transform_graph (+ its _ws_floats) /
-                               pti_umap_transform_layout appended in the same way. */
+                               pti_umap_transform_layout appended in the same way.
+                               Still 5: pti_display_planes appended in the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -677,6 +678,30 @@ int pti_umap_transform_graph(const int* knn_idx, const float* knn_dist, int m, i
 int pti_umap_transform_layout(const int* knn_idx, const int* rate, int m, int k, const float* y_train, int n, const float* y_in,
                               float* y_out, double a, double b, double initial_alpha, int n_epochs, int epoch_begin,
                               int epoch_end, uint32_t seed, int negative_sample_rate, pti_stream_t s);
+
+/* ---- display normalisation of image planes (the reference's normalize_batch_for_display, src/pti_ldm_vae/utils/
+ *      visualization.py:6-40, plus the rotation and the side-by-side canvas of train_vae.py:536-549,610-626;
+ *      csrc/display.hip) ----
+ * a, b: contiguous fp32 [n][h][w] (b may be NULL for nsrc = 1).  nsrc = 1, 2 or 3 picks the sources of image i: a[i]; a[i],
+ * b[i]; a[i], b[i], fabsf(a[i] - b[i]) (formed in fp32).  Plane (i, s) is normalised on its own:
+ *   foreground = v != 0 (so -0.0 is background); cnt = its size; cnt == 0: the plane is all 0 and its stats are {0, 0, 0};
+ *   percentile q (numpy's linear method) of the SORTED foreground values s[0 .. cnt): vi = (cnt - 1) q / 100 in fp64,
+ *   lo = floor(vi), hi = min(lo + 1, cnt - 1), p = s[lo] + (s[hi] - s[lo]) (vi - lo) in fp64 -- the order statistics are
+ *   exact (a radix select on the values: ties are harmless);
+ *   x = clip((v - p_low) / (p_high - p_low + 1e-8), 0, 1) in fp64, rounded to fp32 once; x < 1e-3f -> 0; background -> 0;
+ *   the 8-bit value is (uint8_t)(x * 255.0f), truncated.
+ * The plane is then rotated by rot_k quarter turns like torch.rot90(k = rot_k, dims = [H, W]) (0 .. 3; (ho, wo) = (h, w) for
+ * even rot_k, (w, h) for odd) and stored in columns [s wo, (s + 1) wo) of image i of the canvas
+ * out_f32 / out_u8 [n][ho][nsrc wo] -- torch.cat([rot90(a), rot90(b), rot90(|a - b|)], dim = 2).  Either canvas may be
+ * NULL, not both; they must not overlap the inputs.  stats: fp64 [n nsrc][3] = {cnt, p_low, p_high}, always written,
+ * 8-byte aligned.  low, high: percentiles, 0 <= low <= high <= 100.
+ * Inputs must be FINITE: nothing is promised for NaN or Inf.  One launch, one workgroup per plane, no workspace, no
+ * atomics on global memory, no host synchronisation: capturable, and bitwise reproducible.
+ * Refused before any launch: null a / stats / both canvases, b missing for nsrc >= 2, nsrc outside 1 .. 3, a dimension < 1,
+ * rot_k outside 0 .. 3, percentiles outside 0 <= low <= high <= 100, a misaligned buffer (PTI_EINVAL); h or w > 4096,
+ * n nsrc > 65535 (PTI_EUNSUPPORTED).                                                                                      */
+int pti_display_planes(const float* a, const float* b, int n, int h, int w, int nsrc, double low, double high, int rot_k,
+                       float* out_f32, uint8_t* out_u8, double* stats, pti_stream_t s);
 
 #ifdef __cplusplus
 }

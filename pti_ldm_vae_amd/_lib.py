@@ -180,6 +180,7 @@ SIGNATURES = {
     "pti_umap_transform_graph_ws_floats": (_I64, [_I, _I, _I]),
     "pti_umap_transform_graph": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "pti_umap_transform_layout": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _D, _D, _D, _I, _I, _I, _U32, _I, _P]),
+    "pti_display_planes": (_I, [_P, _P, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1226,6 +1226,71 @@ def mask_geometry(src, offsets, hw, *, elem, max_h, sample_rows, bottom_offsets,
     return bbox, bbox_widths, bottom_widths
 
 
+# ---- display normalisation (csrc/display.hip; include/pti_vae.h "display normalisation") --------------------------------
+DISPLAY_MAX_EDGE, DISPLAY_MAX_PLANES = 4096, 65535   # the bounds of pti_display_planes
+
+
+def display_planes(a, b=None, *, nsrc=None, low=2, high=98, rot90=0, dtype=torch.uint8):
+    """``normalize_batch_for_display`` of every plane, rotated and laid side by side, in one launch
+    (``pti_display_planes``) -> ``(canvas, stats)``.
+
+    ``a`` / ``b``: fp32 device images ``[n, h, w]`` or ``[n, 1, h, w]`` of one shape.  ``nsrc`` picks the sources per image:
+    1 = ``a``; 2 = ``a, b``; 3 = ``a, b, |a - b|`` (default: 1 without ``b``, 2 with it).  Every plane is mapped on its own
+    from the ``low`` .. ``high`` percentile of its non-zero pixels to 0 .. 1 (clipped, below 1e-3 -> 0, zeros stay 0), turned
+    by ``rot90`` quarter turns like ``torch.rot90(k, dims=[-2, -1])`` and written into columns ``[s * wo, (s + 1) * wo)`` of
+    ``canvas [n, ho, nsrc * wo]``: ``dtype`` float32 holds the mapped value, uint8 holds ``trunc(value * 255)``.
+    ``stats``: float64 ``[n, nsrc, 3]`` = ``{non-zero count, p_low, p_high}`` on the device.  Inputs must be finite.  Runs
+    on the current stream, no host sync, no scratch (one workgroup per plane keeps everything in LDS)."""
+    who = "display_planes"
+    for name, t in (("a", a), ("b", b)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != F32):
+            raise TypeError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if nsrc is None:
+        nsrc = 1 if b is None else 2
+    if nsrc not in (1, 2, 3):
+        raise ValueError(f"{who}: nsrc must be 1, 2 or 3, got {nsrc!r}")
+    if nsrc >= 2 and b is None:
+        raise ValueError(f"{who}: nsrc = {nsrc} needs b")
+    low, high = float(low), float(high)
+    if not 0.0 <= low <= high <= 100.0:
+        raise ValueError(f"{who}: percentiles must satisfy 0 <= low <= high <= 100, got {low}, {high}")
+    rot90 = int(rot90)
+    if not 0 <= rot90 <= 3:
+        raise ValueError(f"{who}: rot90 must be 0, 1, 2 or 3, got {rot90}")
+    if dtype not in (torch.uint8, F32):
+        raise TypeError(f"{who}: dtype must be torch.uint8 or torch.float32, got {dtype}")
+    if a.dim() == 4 and a.shape[1] == 1:
+        a = a[:, 0]
+    if b is not None and b.dim() == 4 and b.shape[1] == 1:
+        b = b[:, 0]
+    if a.dim() != 3 or (b is not None and b.shape != a.shape):
+        raise ValueError(f"{who}: expected [n, h, w] or [n, 1, h, w] images of one shape, got {tuple(a.shape)}"
+                         + (f" / {tuple(b.shape)}" if b is not None else ""))
+    if nsrc == 1:
+        b = None
+    _chk(a, F32, f"{who}: a")
+    if b is not None:
+        _chk(b, F32, f"{who}: b")
+        if b.device != a.device:
+            raise ValueError(f"{who}: a and b must be on one device")
+    n, h, w = a.shape
+    if n < 1 or not (1 <= h <= DISPLAY_MAX_EDGE and 1 <= w <= DISPLAY_MAX_EDGE) or n * nsrc > DISPLAY_MAX_PLANES:
+        raise ValueError(f"{who}: unsupported shape {tuple(a.shape)} with nsrc = {nsrc} (1 <= h, w <= {DISPLAY_MAX_EDGE}, "
+                         f"1 <= n * nsrc <= {DISPLAY_MAX_PLANES})")
+    ho, wo = (w, h) if rot90 & 1 else (h, w)
+    canvas = torch.empty((n, ho, nsrc * wo), dtype=dtype, device=a.device)
+    stats = torch.empty((n, nsrc, 3), dtype=torch.float64, device=a.device)
+    prof = KERNEL_PROFILE
+    rec = None if prof is None else _prof_begin(prof)
+    L.check(L.lib().pti_display_planes(_ptr(a), _ptr(b), n, h, w, nsrc, low, high, rot90,
+                                       _ptr(canvas) if dtype == F32 else None, _ptr(canvas) if dtype == torch.uint8 else None,
+                                       _ptr(stats), _stream()), "pti_display_planes")
+    if rec is not None:   # four select passes over the plane's values (two inputs for |a - b|) and one map pass
+        reads = 4.0 * a.numel() * (nsrc + (nsrc == 3))
+        _prof_end(rec, 0.0, 5 * reads + canvas.numel() * canvas.element_size(), ("display", nsrc, h, w, rot90, n))
+    return canvas, stats
+
+
 # ---- PatchDiscriminator passes (csrc/discriminator.hip; include/pti_vae.h "PatchDiscriminator") -----------------------
 def pd_out_hw(h, w, stride):
     return (h + 2 - 4) // stride + 1, (w + 2 - 4) // stride + 1

@@ -27,7 +27,12 @@ What is different, on purpose:
     in effect is the first record of ``metrics.jsonl``); ``--synthetic N`` trains on N seeded synthetic images of the configured patch size (z-scored
     elliptical foreground, zero background; U(0,1) attributes), sharded across ranks like ``DistributedSampler``;
   * logging goes to ``<run_dir>/metrics.jsonl`` with the reference's W&B metric names
-    (``train/recon_loss`` ... ``val/loss_total``), one host sync per ``--log-every`` steps.
+    (``train/recon_loss`` ... ``val/loss_total``), one host sync per ``--log-every`` steps;
+  * the validation pictures (``validation_samples/epoch_E/{originale,reconstruction,diff}/stepNNN.tif`` from epoch 10 on,
+    every 5th epoch, train_vae.py:536-549,610-618) are written as the reference writes them, without a host sync per
+    validation step; the validation triplet it logs to W&B every 20 epochs (:620-626) is written as
+    ``triplets/val_epochEEE_stepSSS.png`` from one ``pti_display_planes`` launch (``utils/validation_samples.py``;
+    ``--val-samples-start / --val-samples-every / --val-triplet-every``).  The train-step triplet is not written.
 """
 from __future__ import annotations
 
@@ -44,6 +49,7 @@ from .models import PatchDiscriminator, PerceptualLoss, VAEModel, compute_total_
 from .trainer import ARSettings, VAETrainer, prepare_batch
 from .utils import read_config, resolve_ar_settings
 from .utils.distributed import setup_ddp
+from .utils.validation_samples import ValidationSampleWriter
 
 
 def parse_args(argv=None):
@@ -67,6 +73,12 @@ def parse_args(argv=None):
     p.add_argument("--adv-start-epoch", type=int, default=6,
                    help="first epoch with the adversarial branch on (the reference hard-codes `epoch > 5`)")
     p.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
+    p.add_argument("--val-samples-start", type=int, default=10,
+                   help="first epoch whose validation pass writes validation_samples/ TIFs (the reference hard-codes 10)")
+    p.add_argument("--val-samples-every", type=int, default=5,
+                   help="write them every N-th epoch (the reference hard-codes 5); 0: never")
+    p.add_argument("--val-triplet-every", type=int, default=20,
+                   help="write one [input | reconstruction | |difference|] PNG under triplets/ every N-th epoch; 0: never")
     return p.parse_args(argv)
 
 
@@ -287,6 +299,14 @@ def main(argv=None):
     if log is not None:     # first record of the run: the augmentation policy in effect (null: none)
         log.write(json.dumps({"augment": policy.to_dict() if policy is not None else None}) + "\n")
         log.flush()
+    samples = None      # validation pictures: rank 0 only, like the reference
+    if rank == 0 and (args.val_samples_every > 0 or args.val_triplet_every > 0):
+        if args.autoencoder_def["in_channels"] != 1:
+            print("[INFO] validation samples are written for single-channel images only: disabled (in_channels = "
+                  f"{args.autoencoder_def['in_channels']})")
+        else:
+            samples = ValidationSampleWriter(args.run_dir, start=args.val_samples_start, every=args.val_samples_every,
+                                             triplet_every=args.val_triplet_every)
     kl_w, max_epochs, val_interval = tr["kl_weight"], tr["max_epochs"], tr["val_interval"]
     for epoch in range(start_epoch, max_epochs):
         t0 = time.time()
@@ -313,9 +333,12 @@ def main(argv=None):
         if epoch % val_interval == 0:
             rsum = ksum = asum = gsum = psum = torch.zeros((), device=device)
             nb = 0
+            keep = samples is not None and samples.begin(epoch)
             for batch in data.batches(epoch, train=False):
                 images, attrs = prepare_batch(batch, device, ar_enabled)
-                v, _ = trainer.eval_losses(images, attributes=attrs, adversarial=adv_on)
+                v, recon = trainer.eval_losses(images, attributes=attrs, adversarial=adv_on)
+                if keep:        # queues device work only; the files are written after the synchronize below
+                    samples.add(nb, images, recon)
                 rsum, ksum, nb = rsum + v["recon"], ksum + v["kl"], nb + 1
                 if adv_on:
                     gsum = gsum + v["adv_gen"]
@@ -330,6 +353,8 @@ def main(argv=None):
                                            ar_vae_enabled=ar_enabled)
             torch.cuda.synchronize()
             dt = time.time() - t0
+            if keep:
+                samples.flush(epoch)
             if rank == 0:
                 print(f"Epoch {epoch} val_loss: {val_recon:.4f} | Time: {dt:.1f}s | {seen * world / dt:.1f} img/s")
                 rec = {"epoch": epoch, "val/recon_loss": val_recon, "val/kl_loss": val_kl, "val/loss_total": val_total,
