@@ -703,6 +703,31 @@ int pti_umap_transform_layout(const int* knn_idx, const int* rate, int m, int k,
 int pti_display_planes(const float* a, const float* b, int n, int h, int w, int nsrc, double low, double high, int rot_k,
                        float* out_f32, uint8_t* out_u8, double* stats, pti_stream_t s);
 
+/* ---- attribute-ordering report of an AR-VAE (the full-set counterpart of pti_ar_vae_loss above; what the reference only
+ *      shows by eye in vae_scripts/analyze_ar_channels.py; csrc/rank_agreement.hip) ----
+ * zt: fp32 [l][ldz], CHANNEL-major per-image latent code z[c][i] (z_mu averaged over the map); attrs: fp32 [na][lda]
+ * attribute values; row strides in ELEMENTS (ldz, lda >= n); channels / deltas: HOST arrays [na], copied into the launch --
+ * channels[q] = the latent channel attribute q regularises (negative: no loss for that attribute), deltas[q] its tanh slope.
+ * Every unordered pair i < j falls, for every (q, c), into exactly one of five classes; signs are decided by comparing the
+ * two floats (>, <), never by subtracting (the library is built with -ffast-math):
+ *   0 concordant: a_j != a_i, z_j != z_i, same sign       1 discordant: a_j != a_i, z_j != z_i, opposite signs
+ *   2 z_tied:     a_j != a_i, z_j == z_i                   3 a_tied:     a_j == a_i, z_j != z_i        4 both_tied
+ * counts: int64 [na][l][5] in that order, EXACT; the five sum to n (n - 1) / 2.
+ * loss_sum: fp64 [na] = sum over the unordered pairs with a_i != a_j of (tanh(delta_q (z_j - z_i)) - sign(a_j - a_i))^2 with
+ *   z of channel channels[q] (0 for a negative channel): the summand of pti_ar_vae_loss, which runs over ORDERED pairs -- the
+ *   term is symmetric, so loss_sum / (concordant + discordant + z_tied) is the same mean.  The summand is formed in fp64
+ *   from the fp32 inputs and added in fp64 in one fixed order.
+ * Two launches (256 x 256 tiles of the upper triangle, then a fold of the per-workgroup partials in tile order): no atomics,
+ * bitwise reproducible, on the caller's stream without a host synchronisation.  Inputs must be FINITE (a NaN ties).
+ * workspace: pti_rank_agreement_ws_bytes(n, l, na) bytes, 8-byte aligned, ws_bytes = its size (pure host arithmetic;
+ * 0 = unsupported shape).  Refused before any launch: null pointers, n < 2, l or na < 1, a row stride below n,
+ * channels[q] >= l, a misaligned buffer, a misaligned or short workspace (PTI_EINVAL); n > 32768, l > 16, na > 16
+ * (PTI_EUNSUPPORTED).                                                                                                   */
+int64_t pti_rank_agreement_ws_bytes(int n, int l, int na);
+int pti_rank_agreement(const float* zt, int64_t ldz, const float* attrs, int64_t lda, int n, int l, int na,
+                       const int32_t* channels, const float* deltas, int64_t* counts, double* loss_sum, void* workspace,
+                       int64_t ws_bytes, pti_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

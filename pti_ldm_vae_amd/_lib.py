@@ -181,6 +181,8 @@ SIGNATURES = {
     "pti_umap_transform_graph": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "pti_umap_transform_layout": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _D, _D, _D, _I, _I, _I, _U32, _I, _P]),
     "pti_display_planes": (_I, [_P, _P, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P]),
+    "pti_rank_agreement_ws_bytes": (_I64, [_I, _I, _I]),
+    "pti_rank_agreement": (_I, [_P, _I64, _P, _I64, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(_F), _P, _P, _P, _I64, _P]),
 }
 
 _lib = None

@@ -1291,6 +1291,66 @@ def display_planes(a, b=None, *, nsrc=None, low=2, high=98, rot90=0, dtype=torch
     return canvas, stats
 
 
+# ---- attribute-ordering report (csrc/rank_agreement.hip; include/pti_vae.h "attribute-ordering report") ------------------
+RANK_AGREEMENT_MAX_N, RANK_AGREEMENT_MAX_L, RANK_AGREEMENT_MAX_NA = 32768, 16, 16   # the bounds of pti_rank_agreement
+RANK_CLASSES = ("concordant", "discordant", "z_tied", "a_tied", "both_tied")
+
+
+def rank_agreement(z, attrs, channels, deltas, *, out=None):
+    """Pair-ordering counts of every (attribute, latent channel) over ALL image pairs (``pti_rank_agreement``) ->
+    ``(counts, loss_sum)`` device tensors.
+
+    ``z``: floating-point device matrix ``[N, L]`` (one latent code per image) in any layout -- a transposed view of a
+    channel-major ``[L, N]`` buffer, row stride included, is used in place, anything else is copied once; ``attrs``: ``[na, N]``
+    attribute values with dense rows.  ``channels`` / ``deltas``: ``na`` host values (sequences or CPU tensors; a device
+    tensor is read back, which synchronises): the latent channel attribute ``q`` regularises (negative: none) and its tanh
+    slope.  ``counts``: int64 ``[na, L, 5]``, exact, in ``RANK_CLASSES`` order over the ``N (N - 1) / 2`` unordered pairs;
+    ``loss_sum``: float64 ``[na]``, the AR summand of ``pti_ar_vae_loss`` added over the pairs whose attribute values differ.
+    ``out=(counts, loss_sum)`` are written in place.  2 <= N <= 32768, L <= 16, na <= 16; inputs must be finite.  Runs on
+    the current stream, no host sync; bitwise reproducible; the scratch buffer is cached per (stream, shape)."""
+    who = "rank_agreement"
+    for name, t in (("z", z), ("attrs", attrs)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
+        if not t.is_floating_point():
+            raise TypeError(f"{who}: {name}: expected a floating-point matrix, got {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"{who}: {name}: expected a matrix, got {tuple(t.shape)}")
+    n, l = z.shape
+    na = attrs.shape[0]
+    if attrs.shape[1] != n or attrs.device != z.device:
+        raise ValueError(f"{who}: z {tuple(z.shape)} needs attrs [na, {n}] on {z.device}, got {tuple(attrs.shape)} on {attrs.device}")
+    if not (2 <= n <= RANK_AGREEMENT_MAX_N and 1 <= l <= RANK_AGREEMENT_MAX_L and 1 <= na <= RANK_AGREEMENT_MAX_NA):
+        raise ValueError(f"{who}: unsupported shape z {tuple(z.shape)} attrs {tuple(attrs.shape)} (2 <= N <= {RANK_AGREEMENT_MAX_N}, "
+                         f"1 <= L <= {RANK_AGREEMENT_MAX_L}, 1 <= na <= {RANK_AGREEMENT_MAX_NA})")
+    zt = z.t()                                               # [L, N]: the kernel reads channel-major rows
+    if zt.dtype != F32:
+        zt = zt.to(F32)
+    if zt.stride(1) != 1 or zt.stride(0) < n:
+        zt = zt.contiguous()
+    attrs = _rows(attrs, f"{who}: attrs")
+    channels = [int(v) for v in (channels.tolist() if isinstance(channels, torch.Tensor) else channels)]
+    deltas = [float(v) for v in (deltas.tolist() if isinstance(deltas, torch.Tensor) else deltas)]
+    if len(channels) != na or len(deltas) != na:
+        raise ValueError(f"{who}: channels / deltas must hold one value per attribute ({na}), got {len(channels)} / {len(deltas)}")
+    if any(c >= l for c in channels):
+        raise ValueError(f"{who}: channels {channels} must lie below the {l} latent channels")
+    if out is None:
+        out = (None, None)
+    counts = _out(out[0], (na, l, 5), I64, z.device, f"{who}: out[0] (counts)")
+    loss_sum = _out(out[1], (na,), torch.float64, z.device, f"{who}: out[1] (loss_sum)")
+    nbytes = L.lib().pti_rank_agreement_ws_bytes(n, l, na)
+    if nbytes <= 0:
+        raise ValueError(f"{who}: unsupported shape z {tuple(z.shape)} attrs {tuple(attrs.shape)}")
+    stream = _stream()
+    ws = _scratch("rank", (n, l, na), (nbytes + 3) // 4, z.device, stream)
+    ldz, lda = (zt.stride(0) if l > 1 else n), (attrs.stride(0) if na > 1 else n)   # a single row's stride means nothing
+    L.check(L.lib().pti_rank_agreement(_ptr(zt), ldz, _ptr(attrs), lda, n, l, na,
+                                       (C.c_int32 * na)(*channels), (C.c_float * na)(*deltas), _ptr(counts), _ptr(loss_sum),
+                                       _ptr(ws), ws.numel() * 4, stream), "pti_rank_agreement")
+    return counts, loss_sum
+
+
 # ---- PatchDiscriminator passes (csrc/discriminator.hip; include/pti_vae.h "PatchDiscriminator") -----------------------
 def pd_out_hw(h, w, stride):
     return (h + 2 - 4) // stride + 1, (w + 2 - 4) // stride + 1
