@@ -728,6 +728,38 @@ int pti_rank_agreement(const float* zt, int64_t ldz, const float* attrs, int64_t
                        const int32_t* channels, const float* deltas, int64_t* counts, double* loss_sum, void* workspace,
                        int64_t ws_bytes, pti_stream_t s);
 
+/* ---- disentanglement report: average ranks, their moments, joint histograms (csrc/disentanglement.hip) ----
+ * Three integer primitives; every result is a count or a 64-bit integer sum, so it is EXACT, independent of the order of
+ * evaluation and of row padding, and bitwise reproducible.  No two floats are ever subtracted (the library is built with
+ * -ffast-math): values are compared, as floats or through their order-preserving integer keys.  All launches go to the
+ * caller's stream without a host synchronisation.  Inputs must be FINITE: nothing is promised for the rank of a NaN.
+ *
+ * pti_tied_ranks: cols fp32 [m][ld] (row stride in ELEMENTS, ld >= n) -> rank2 int32 [m][n] (dense),
+ *   rank2[c][i] = 2 #{j : x_j < x_i} + #{j : x_j == x_i} + 1 = twice the average rank (scipy rankdata "average");
+ *   -0.0 ties with 0.0.  One launch, no workspace.
+ * pti_rank_moments: rank2 int32 [m][n] as written above -> sums int64 [m] = sum_i rank2[a][i], gram int64 [m][m] =
+ *   sum_i rank2[a][i] rank2[b][i] (64-bit products and sums).  One launch, no workspace.
+ * Both refuse before any launch: null pointers, n < 2, m < 1, ld < n, a misaligned buffer (PTI_EINVAL); n > 32768, m > 32
+ * (PTI_EUNSUPPORTED).                                                                                                    */
+int pti_tied_ranks(const float* cols, int64_t ld, int n, int m, int32_t* rank2, pti_stream_t s);
+int pti_rank_moments(const int32_t* rank2, int n, int m, int64_t* sums, int64_t* gram, pti_stream_t s);
+
+/* pti_joint_histogram: zt fp32 [l][ldz] channel-major codes and attrs fp32 [na][lda] as in pti_rank_agreement; edges_z fp64
+ * [l][bins] / edges_a fp64 [na][bins]: the LEFT edges of every column's bins, ascending (device memory).
+ *   bin(x) = #{k : edges[k] <= (double)x} - 1, so the last bin is closed on the right and takes everything above it;
+ *   a value below edges[0] has no bin: it is stored as 255 and counted nowhere (the caller is expected to refuse it).
+ * bins_z uint8 [l][n], bins_a uint8 [na][n] (dense); counts int32 [na][l][bins][bins], indexed [q][c][bin_a][bin_z]: every
+ * table sums to n; its row / column sums are the marginals.
+ * Three launches: bin indices; per-workgroup tables in LDS (integer LDS adds) over chunks of 2048 rows; a fold of the chunks
+ * in chunk order.  No atomics on global memory.  workspace: pti_joint_histogram_ws_bytes(n, l, na, bins) bytes, 4-byte
+ * aligned, ws_bytes = its size (pure host arithmetic; 0 = unsupported shape).  Refused before any launch: null pointers,
+ * n < 2, bins < 2, l or na < 1, a row stride below n, a misaligned buffer, a misaligned or short workspace (PTI_EINVAL);
+ * n > 32768, l > 16, na > 16, bins > 32 (PTI_EUNSUPPORTED).                                                               */
+int64_t pti_joint_histogram_ws_bytes(int n, int l, int na, int bins);
+int pti_joint_histogram(const float* zt, int64_t ldz, const float* attrs, int64_t lda, int n, int l, int na, int bins,
+                        const double* edges_z, const double* edges_a, uint8_t* bins_z, uint8_t* bins_a, int32_t* counts,
+                        void* workspace, int64_t ws_bytes, pti_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

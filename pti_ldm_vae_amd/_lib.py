@@ -183,6 +183,10 @@ SIGNATURES = {
     "pti_display_planes": (_I, [_P, _P, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P]),
     "pti_rank_agreement_ws_bytes": (_I64, [_I, _I, _I]),
     "pti_rank_agreement": (_I, [_P, _I64, _P, _I64, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(_F), _P, _P, _P, _I64, _P]),
+    "pti_tied_ranks": (_I, [_P, _I64, _I, _I, _P, _P]),
+    "pti_rank_moments": (_I, [_P, _I, _I, _P, _P, _P]),
+    "pti_joint_histogram_ws_bytes": (_I64, [_I, _I, _I, _I]),
+    "pti_joint_histogram": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I64, _P]),
 }
 
 _lib = None

@@ -1351,6 +1351,132 @@ def rank_agreement(z, attrs, channels, deltas, *, out=None):
     return counts, loss_sum
 
 
+# ---- disentanglement report (csrc/disentanglement.hip; include/pti_vae.h "disentanglement report") ----------------------
+DISENT_MAX_N, DISENT_MAX_COLS, DISENT_MAX_BINS = 32768, 32, 32   # the bounds of pti_tied_ranks / pti_joint_histogram
+
+
+def tied_ranks(cols, *, out=None):
+    """Twice the average rank of every value within its column (``pti_tied_ranks``) -> int32 ``[M, N]`` device tensor.
+
+    ``cols``: floating-point device matrix ``[M, N]``, one column of ``N`` values per ROW; rows with a dense last dimension
+    (a row-strided slice included) are used in place, anything else is copied once.  ``rank2[m, i] = 2 #{j: x_j < x_i} +
+    #{j: x_j == x_i} + 1``, exactly ``2 * scipy.stats.rankdata(x, "average")``; ``-0.0`` ties with ``0.0``.  ``out`` is
+    written in place.  2 <= N <= 32768, 1 <= M <= 32; inputs must be finite.  Current stream, no host sync, exact."""
+    who = "tied_ranks"
+    cols = _rows(cols, f"{who}: cols")
+    m, n = cols.shape
+    if not (2 <= n <= DISENT_MAX_N and 1 <= m <= DISENT_MAX_COLS):
+        raise ValueError(f"{who}: unsupported shape cols {tuple(cols.shape)} (2 <= N <= {DISENT_MAX_N}, 1 <= M <= {DISENT_MAX_COLS})")
+    rank2 = _out(out, (m, n), torch.int32, cols.device, f"{who}: out (rank2)")
+    prof = KERNEL_PROFILE
+    rec = None if prof is None else _prof_begin(prof)
+    L.check(L.lib().pti_tied_ranks(_ptr(cols), cols.stride(0) if m > 1 else n, n, m, _ptr(rank2), _stream()), "pti_tied_ranks")
+    if rec is not None:   # two compares and two adds per (i, j); every column is read once per row tile
+        _prof_end(rec, 0.0, 4.0 * m * n * (1 + (n + 255) // 256), ("tied_ranks", m, n))
+    return rank2
+
+
+def rank_moments(rank2, *, out=None):
+    """Column sums and the Gram matrix of ``tied_ranks``' output (``pti_rank_moments``) -> ``(sums, gram)``: int64 ``[M]``
+    and int64 ``[M, M]`` device tensors, ``gram[a, b] = sum_i rank2[a, i] * rank2[b, i]`` in 64-bit integers: exact.
+    ``rank2``: contiguous int32 ``[M, N]``.  ``out=(sums, gram)`` are written in place.  Current stream, no host sync."""
+    who = "rank_moments"
+    if not isinstance(rank2, torch.Tensor) or not rank2.is_cuda:
+        raise ValueError(f"{who}: rank2: expected a CUDA(HIP) tensor")
+    if rank2.dtype != torch.int32:
+        raise TypeError(f"{who}: rank2: expected torch.int32, got {rank2.dtype}")
+    if rank2.dim() != 2 or not rank2.is_contiguous():
+        raise ValueError(f"{who}: rank2: expected a contiguous [M, N] matrix, got {tuple(rank2.shape)} strides {rank2.stride()}")
+    m, n = rank2.shape
+    if not (2 <= n <= DISENT_MAX_N and 1 <= m <= DISENT_MAX_COLS):
+        raise ValueError(f"{who}: unsupported shape rank2 {tuple(rank2.shape)} (2 <= N <= {DISENT_MAX_N}, 1 <= M <= {DISENT_MAX_COLS})")
+    if out is None:
+        out = (None, None)
+    sums = _out(out[0], (m,), I64, rank2.device, f"{who}: out[0] (sums)")
+    gram = _out(out[1], (m, m), I64, rank2.device, f"{who}: out[1] (gram)")
+    prof = KERNEL_PROFILE
+    rec = None if prof is None else _prof_begin(prof)
+    L.check(L.lib().pti_rank_moments(_ptr(rank2), n, m, _ptr(sums), _ptr(gram), _stream()), "pti_rank_moments")
+    if rec is not None:   # the pairs a <= b, two columns read per pair
+        _prof_end(rec, 0.0, 4.0 * n * m * (m + 1), ("rank_moments", m, n))
+    return sums, gram
+
+
+def _edges(t, rows, bins, device, name):
+    """Left bin edges ``[rows, bins]`` (tensor, array or nested sequence, host or device) as a contiguous fp64 device tensor."""
+    t = torch.as_tensor(t)
+    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] != bins:
+        raise ValueError(f"{name}: expected [{rows}, {bins}] left edges, got {tuple(t.shape)}")
+    if not t.is_floating_point():
+        raise TypeError(f"{name}: expected floating-point edges, got {t.dtype}")
+    return t.to(device=device, dtype=torch.float64).contiguous()
+
+
+def joint_histogram(z, attrs, edges_z, edges_a, *, out=None):
+    """Joint histograms of every (attribute, latent channel) over fixed bins (``pti_joint_histogram``) ->
+    ``(bins_z, bins_a, counts)`` device tensors.
+
+    ``z``: floating-point device matrix ``[N, L]`` in any layout -- a transposed view of a channel-major ``[L, N]`` buffer,
+    row stride included, is used in place, anything else is copied once; ``attrs``: ``[na, N]`` with dense rows.
+    ``edges_z`` ``[L, B]`` / ``edges_a`` ``[na, B]``: the ascending LEFT edges of every column's bins (host or device; used as
+    fp64).  ``bin(x) = #{k: edges[k] <= x} - 1``: the last bin takes everything from its edge upwards.  ``bins_z`` uint8
+    ``[L, N]``, ``bins_a`` uint8 ``[na, N]``; ``counts`` int32 ``[na, L, B, B]`` indexed ``[q, c, bin_a, bin_z]``, exact; every
+    table sums to ``N`` and its row / column sums are the marginals.  ``out=(bins_z, bins_a, counts)`` are written in place.
+    A value below its column's first edge has no bin and is refused with a ValueError -- the one check that reads a
+    device result back (one host synchronisation per call).  2 <= N <= 32768, L <= 16, na <= 16, 2 <= B <= 32.  Runs on
+    the current stream; bitwise reproducible; the scratch buffer is cached per (stream, shape)."""
+    who = "joint_histogram"
+    for name, t in (("z", z), ("attrs", attrs)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
+        if not t.is_floating_point():
+            raise TypeError(f"{who}: {name}: expected a floating-point matrix, got {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"{who}: {name}: expected a matrix, got {tuple(t.shape)}")
+    n, l = z.shape
+    na = attrs.shape[0]
+    if attrs.shape[1] != n or attrs.device != z.device:
+        raise ValueError(f"{who}: z {tuple(z.shape)} needs attrs [na, {n}] on {z.device}, got {tuple(attrs.shape)} on {attrs.device}")
+    edges_z = torch.as_tensor(edges_z)
+    bins = int(edges_z.shape[1]) if edges_z.dim() == 2 else 0
+    if not (2 <= n <= DISENT_MAX_N and 1 <= l <= 16 and 1 <= na <= 16 and 2 <= bins <= DISENT_MAX_BINS):
+        raise ValueError(f"{who}: unsupported shape z {tuple(z.shape)} attrs {tuple(attrs.shape)} bins {bins} (2 <= N <= "
+                         f"{DISENT_MAX_N}, 1 <= L <= 16, 1 <= na <= 16, 2 <= B <= {DISENT_MAX_BINS})")
+    edges_z = _edges(edges_z, l, bins, z.device, f"{who}: edges_z")
+    edges_a = _edges(edges_a, na, bins, z.device, f"{who}: edges_a")
+    zt = z.t()                                               # [L, N]: the kernel reads channel-major rows
+    if zt.dtype != F32:
+        zt = zt.to(F32)
+    if zt.stride(1) != 1 or zt.stride(0) < n:
+        zt = zt.contiguous()
+    attrs = _rows(attrs, f"{who}: attrs")
+    low = torch.cat([zt.amin(1).double() < edges_z[:, 0], attrs.amin(1).double() < edges_a[:, 0]])
+    if bool(low.any()):                                      # the host synchronisation of this wrapper
+        col = int(low.nonzero()[0])
+        raise ValueError(f"{who}: {'channel ' + str(col) if col < l else 'attribute ' + str(col - l)} holds a value below its "
+                         "first edge: it has no bin")
+    if out is None:
+        out = (None, None, None)
+    bins_z = _out(out[0], (l, n), torch.uint8, z.device, f"{who}: out[0] (bins_z)")
+    bins_a = _out(out[1], (na, n), torch.uint8, z.device, f"{who}: out[1] (bins_a)")
+    counts = _out(out[2], (na, l, bins, bins), torch.int32, z.device, f"{who}: out[2] (counts)")
+    nbytes = L.lib().pti_joint_histogram_ws_bytes(n, l, na, bins)
+    if nbytes <= 0:
+        raise ValueError(f"{who}: unsupported shape z {tuple(z.shape)} attrs {tuple(attrs.shape)} bins {bins}")
+    stream = _stream()
+    ws = _scratch("jhist", (n, l, na, bins), (nbytes + 3) // 4, z.device, stream)
+    ldz, lda = (zt.stride(0) if l > 1 else n), (attrs.stride(0) if na > 1 else n)   # a single row's stride means nothing
+    prof = KERNEL_PROFILE
+    rec = None if prof is None else _prof_begin(prof)
+    L.check(L.lib().pti_joint_histogram(_ptr(zt), ldz, _ptr(attrs), lda, n, l, na, bins, _ptr(edges_z), _ptr(edges_a),
+                                        _ptr(bins_z), _ptr(bins_a), _ptr(counts), _ptr(ws), ws.numel() * 4, stream),
+            "pti_joint_histogram")
+    if rec is not None:   # the values once, the bin indices once per partner column, the partial tables twice
+        _prof_end(rec, 0.0, 5.0 * n * (l + na) + 2.0 * n * l * na + 2.0 * nbytes + 4.0 * counts.numel(),
+                  ("joint_histogram", l, na, n, bins))
+    return bins_z, bins_a, counts
+
+
 # ---- PatchDiscriminator passes (csrc/discriminator.hip; include/pti_vae.h "PatchDiscriminator") -----------------------
 def pd_out_hw(h, w, stride):
     return (h + 2 - 4) // stride + 1, (w + 2 - 4) // stride + 1
