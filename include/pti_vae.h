@@ -42,7 +42,8 @@ typedef void* pti_stream_t; /* hipStream_t */
                                in the same way.
                                Still 5: pti_umap_knn_cross / pti_umap_transform_graph (+ its _ws_floats) /
                                pti_umap_transform_layout appended in the same way.
-                               Still 5: pti_display_planes appended in the same way. */
+                               Still 5: pti_display_planes appended in the same way.
+                               Still 5: pti_mask_compare / pti_mask_compare_ws_bytes appended in the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -759,6 +760,40 @@ int64_t pti_joint_histogram_ws_bytes(int n, int l, int na, int bins);
 int pti_joint_histogram(const float* zt, int64_t ldz, const float* attrs, int64_t lda, int n, int l, int na, int bins,
                         const double* edges_z, const double* edges_a, uint8_t* bins_z, uint8_t* bins_a, int32_t* counts,
                         void* workspace, int64_t ws_bytes, pti_stream_t s);
+
+/* ---- shape comparison of image pairs (reference src/pti_ldm_vae/analysis/metrics.py:143-209,312-398: generate_clean_mask,
+ *      dice_coefficient, iou, compute_object_dimensions, calculate_psnr; csrc/mask_compare.hip) ----
+ * gt, pred: fp32 [n][h][w], dense, FINITE; 1 <= n, 1 <= h, w <= PTI_MASK_COMPARE_MAX_EDGE; threshold >= 0.
+ * Per image two masks, by ordinary float compares: G = (gt != 0), R = (pred > threshold) | (pred < -threshold), so a value
+ * exactly at +-threshold is background.  For a mask M:
+ *   K(M): its 8-connected component with the most pixels; among equals the one that holds the smallest row-major pixel
+ *         index; none for an empty M.
+ *   F(M): K plus every pixel outside K that cannot reach the image border by 4-connected steps over pixels outside K (a ring
+ *         of background is thought round the image) = scipy.ndimage.binary_fill_holes(K); smaller components that lie in a
+ *         hole of K are part of it.                                                    P = F(R) below.
+ * counts: int32 [n][PTI_MASK_COMPARE_COLUMNS], the columns in this order:
+ *    0 n_gt = |G|           1 n_pred = |R|         2 components_gt       3 components_pred
+ *    4 kept_gt = |K(G)|     5 kept_pred = |K(R)|   6 filled_pred = |P|   7 intersection = |P and G|   8 union = |P or G|
+ *    9..12  gt_x, gt_y, gt_w, gt_h:         bounding box of K(G)     \  {-1, -1, 0, 0} when the mask is empty
+ *   13..16  pred_x, pred_y, pred_w, pred_h: bounding box of K(R)     /  (the box of F(K) is the box of K)
+ *   17..19  gt_width_upper / _middle / _lower:   pixels of G (the whole mask, not K(G)) in columns [x, x + w) of rows
+ *           y + h / 4, y + h / 2, y + 3 h / 4 of the gt box (integer division); a COUNT, not last - first + 1
+ *   20..22  pred_width_upper / _middle / _lower: the same counts of P in the pred box;   all 0 without a box
+ *   23      status: 0, or 1 when a label-following loop ran out of its step budget (an internal error: every other column
+ *           and all three sums of that row are then 0).  It arrives with the results: nothing is read back by the call.
+ * sums: fp64 [n][3] = { sum over all pixels of (gt - pred P)^2 with the difference formed in fp64,  max(gt),  max(pred P) },
+ *   pred P being pred inside P and 0 elsewhere.  The sum is added in one fixed order: bitwise reproducible.
+ * One launch, one workgroup per image; labelling is a union-find with integer atomicMin on parents kept in the workspace, so
+ * the root of a component is its smallest index whatever the scheduling: every result is independent of the image's place in
+ * the batch and of what the workspace held before.  Runs on the caller's stream without a host synchronisation.
+ * workspace: pti_mask_compare_ws_bytes(n, h, w) bytes, 4-byte aligned, ws_bytes = its size (pure host arithmetic; 0 =
+ * unsupported shape).  Refused before any launch: null pointers, n, h or w < 1, a threshold that is negative or NaN, a
+ * misaligned buffer, a misaligned or short workspace (PTI_EINVAL); h or w above the cap (PTI_EUNSUPPORTED).              */
+#define PTI_MASK_COMPARE_MAX_EDGE 1024
+#define PTI_MASK_COMPARE_COLUMNS 24
+int64_t pti_mask_compare_ws_bytes(int n, int h, int w);
+int pti_mask_compare(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts, double* sums,
+                     void* workspace, int64_t ws_bytes, pti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,11 @@ class WgradJob(C.Structure):
 
 WGRAD_BATCH_MAX = 16   # PTI_WGRAD_BATCH_MAX
 DIRECT_REPACK_MAX = 8  # PTI_DIRECT_REPACK_MAX
+# the int32 columns of pti_mask_compare's counts, in order (include/pti_vae.h "shape comparison")
+MASK_COMPARE_COLUMNS = ("n_gt", "n_pred", "components_gt", "components_pred", "kept_gt", "kept_pred", "filled_pred",
+                        "intersection", "union", "gt_x", "gt_y", "gt_w", "gt_h", "pred_x", "pred_y", "pred_w", "pred_h",
+                        "gt_width_upper", "gt_width_middle", "gt_width_lower",
+                        "pred_width_upper", "pred_width_middle", "pred_width_lower", "status")
 
 
 class DirectRepackEntry(C.Structure):
@@ -187,6 +192,8 @@ SIGNATURES = {
     "pti_rank_moments": (_I, [_P, _I, _I, _P, _P, _P]),
     "pti_joint_histogram_ws_bytes": (_I64, [_I, _I, _I, _I]),
     "pti_joint_histogram": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pti_mask_compare_ws_bytes": (_I64, [_I, _I, _I]),
+    "pti_mask_compare": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _I64, _P]),
 }
 
 _lib = None

@@ -1,0 +1,215 @@
+#!/usr/bin/env python3
+"""Does a generated or reconstructed image have the same SHAPE as its ground truth?  The counterpart of the reference's
+``analysis/metrics.py::ImageComparison.process_all_images``: Dice and IoU of the foreground masks, the object's height and
+its width at three levels, MSE / PSNR against the cleaned prediction, their aggregates with outlier counts, and the share
+of exams within 5 / 10 pixels or above 90 / 95 / 97 %.
+
+    python -m pti_ldm_vae_amd.compare_images --gt-dir edente --pred-dir edente_synth [--output-dir DIR]
+    python -m pti_ldm_vae_amd.compare_images --results-dir inference_vae_<checkpoint>/results_tif
+
+``--gt-dir`` / ``--pred-dir`` pair the ``.tif`` / ``.tiff`` files of two folders by file name (files present in one folder
+only are reported); ``--results-dir`` takes the ``[input | reconstruction]`` files ``inference_vae`` writes: the left half is
+the ground truth, the right half the prediction, and a file of odd width is refused.
+
+The ground-truth mask is ``pixel != 0``; the prediction's is ``|pixel| > --threshold``, cleaned to its largest 8-connected
+component with the holes filled -- the per-pixel work of a batch is one ``ops.mask_compare`` launch (csrc/mask_compare.hip)
+and one copy back; images are grouped by size.  A pair whose sides differ in size, cannot be read, is larger than the
+kernel's 1024-pixel edge or has no foreground on a side is skipped and listed with the reason.
+
+Written to ``--output-dir`` (default ``<input folder>/compare``): ``_metrics.csv`` and ``_dimensions.csv`` in the reference's
+layout (``;``-separated), ``compare_metrics.json`` (per-image rows, aggregates, thresholds, skipped pairs, resolved
+arguments) and, unless ``--no-plot``, ``_metrics_distribution.png``.  Not computed: SSIM (``evaluate_vae`` reports it), the
+VGG16 feature distances, and the reference's straighten / align step."""
+from __future__ import annotations
+
+import argparse
+import json
+import random
+from pathlib import Path
+
+import numpy as np
+
+WHO = "compare_images"
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    parser = argparse.ArgumentParser(description="Shape comparison of ground-truth / prediction image pairs (Dice, IoU, object "
+                                                 "height and widths); MI355X, HIP labelling kernel.")
+    parser.add_argument("--gt-dir", type=Path, default=None, help="folder of ground-truth TIFs (with --pred-dir)")
+    parser.add_argument("--pred-dir", type=Path, default=None, help="folder of predicted TIFs, paired with --gt-dir by file name")
+    parser.add_argument("--results-dir", type=Path, default=None,
+                        help="folder of inference_vae results_tif files: [input | reconstruction] side by side")
+    parser.add_argument("--threshold", type=float, default=0.2, help="a predicted pixel is foreground when |pixel| > this (default: 0.2)")
+    parser.add_argument("--batch-size", type=int, default=64, help="image pairs per kernel launch (default: 64)")
+    parser.add_argument("--num-samples", type=int, default=None, help="compare a random sample of this many pairs (default: all)")
+    parser.add_argument("--output-dir", type=Path, default=None, help="where the report goes (default: <input folder>/compare)")
+    parser.add_argument("--no-plot", action="store_true", help="do not write _metrics_distribution.png")
+    parser.add_argument("--seed", type=int, default=0, help="seed of the --num-samples draw (default: 0)")
+    args = parser.parse_args(argv)
+    pair_mode = args.gt_dir is not None or args.pred_dir is not None
+    if pair_mode and args.results_dir is not None:
+        parser.error("give either --gt-dir with --pred-dir, or --results-dir, not both")
+    if not pair_mode and args.results_dir is None:
+        parser.error("give --gt-dir with --pred-dir, or --results-dir")
+    if pair_mode and (args.gt_dir is None or args.pred_dir is None):
+        parser.error("--gt-dir and --pred-dir go together")
+    if not args.threshold >= 0.0:
+        parser.error(f"--threshold must be >= 0, got {args.threshold}")
+    if args.batch_size < 1:
+        parser.error(f"--batch-size must be >= 1, got {args.batch_size}")
+    if args.num_samples is not None and args.num_samples < 1:
+        parser.error(f"--num-samples must be >= 1, got {args.num_samples}")
+    return args
+
+
+def list_tif_files(path: Path) -> dict[str, Path]:
+    """file name -> file of every ``.tif`` / ``.tiff`` (any letter case) in ``path``, sorted."""
+    if not path.is_dir():
+        raise FileNotFoundError(f"{WHO}: folder does not exist: {path}")
+    return {p.name: p for p in sorted(path.iterdir()) if p.is_file() and p.suffix.lower() in {".tif", ".tiff"}}
+
+
+def list_pairs(args) -> tuple[list, dict]:
+    """-> (``[(name, gt file, pred file or None)]`` in sorted order, ``{"gt_only": [...], "pred_only": [...]}``); a pred
+    file of ``None`` means the one file holds both halves."""
+    if args.results_dir is not None:
+        files = list_tif_files(args.results_dir)
+        return [(name, p, None) for name, p in files.items()], {"gt_only": [], "pred_only": []}
+    gt, pred = list_tif_files(args.gt_dir), list_tif_files(args.pred_dir)
+    unpaired = {"gt_only": sorted(set(gt) - set(pred)), "pred_only": sorted(set(pred) - set(gt))}
+    return [(name, gt[name], pred[name]) for name in sorted(set(gt) & set(pred))], unpaired
+
+
+class OddWidth(Exception):
+    """A --results-dir file that cannot be split in two halves: the run is refused, not the file skipped."""
+
+
+def load_pair(gt_file: Path, pred_file: Path | None):
+    """-> (gt, pred) as 2-D float32 arrays.  ValueError: unreadable, not 2-D or sides of different size (the pair is
+    skipped); OddWidth: a side-by-side file that cannot be halved (the run is refused)."""
+    from .data.tiff import read_tiff
+    if pred_file is None:
+        both = np.asarray(read_tiff(str(gt_file)))
+        if both.ndim != 2:
+            raise ValueError(f"{gt_file.name}: expected a 2-D image, got shape {both.shape}")
+        if both.shape[1] % 2:
+            raise OddWidth(f"{WHO}: {gt_file}: width {both.shape[1]} is odd: not an [input | reconstruction] file")
+        half = both.shape[1] // 2
+        gt, pred = both[:, :half], both[:, half:]
+    else:
+        gt, pred = np.asarray(read_tiff(str(gt_file))), np.asarray(read_tiff(str(pred_file)))
+    if gt.ndim != 2 or pred.ndim != 2:
+        raise ValueError(f"expected 2-D images, got shapes {gt.shape} and {pred.shape}")
+    if gt.shape != pred.shape:
+        raise ValueError(f"Images do not have the same dimensions: {gt.shape} and {pred.shape}")
+    return np.ascontiguousarray(gt, dtype=np.float32), np.ascontiguousarray(pred, dtype=np.float32)
+
+
+def compare_batch(gts: list, preds: list, threshold: float, device):
+    """One launch and ONE copy back for a batch of one shape -> (counts int32 ``[n, 24]``, sums float64 ``[n, 3]``) on the
+    host.  Both outputs are views of one device buffer (3 doubles, then 24 int32 = 12 doubles per image)."""
+    import torch
+
+    from . import ops
+    n = len(gts)
+    gt = torch.from_numpy(np.stack(gts)).to(device)
+    pred = torch.from_numpy(np.stack(preds)).to(device)
+    buf = torch.empty(n * 15, dtype=torch.float64, device=device)
+    sums = buf[:3 * n].view(n, 3)
+    counts = buf[3 * n:].view(torch.int32).view(n, len(ops.MASK_COMPARE_COLUMNS))
+    ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums))
+    host = buf.cpu().numpy()
+    return host[3 * n:].view(np.int32).reshape(n, -1).copy(), host[:3 * n].reshape(n, 3).copy()
+
+
+def run(args, device) -> dict:
+    """The whole report as a dictionary (what ``compare_metrics.json`` holds), files not yet written."""
+    from . import ops
+    from .utils import compare_metrics as M
+    pairs, unpaired = list_pairs(args)
+    if not pairs:
+        raise FileNotFoundError(f"{WHO}: no .tif / .tiff " + ("file in " + str(args.results_dir) if args.results_dir is not None
+                                else f"file name is present in both {args.gt_dir} and {args.pred_dir}"))
+    if args.num_samples is not None and args.num_samples < len(pairs):
+        pairs = sorted(random.Random(args.seed).sample(pairs, args.num_samples))
+    results, buckets = {}, {}
+
+    def flush(shape):
+        names, gts, preds = buckets.pop(shape)
+        counts, sums = compare_batch(gts, preds, args.threshold, device)
+        for name, row, s, m in zip(names, counts, sums, M.pair_metrics(counts, sums, *shape)):
+            results[name] = m if isinstance(m, str) else {"metrics": m, "dimensions": M.dimensions(row),
+                                                          "counts": dict(zip(ops.MASK_COMPARE_COLUMNS, (int(v) for v in row))),
+                                                          "sums": dict(zip(ops.MASK_COMPARE_SUMS, (float(v) for v in s)))}
+
+    for name, gt_file, pred_file in pairs:
+        try:
+            gt, pred = load_pair(gt_file, pred_file)
+            if max(gt.shape) > ops.MASK_COMPARE_MAX_EDGE or min(gt.shape) < 1:
+                raise ValueError(f"image size {gt.shape} is not supported (1 .. {ops.MASK_COMPARE_MAX_EDGE} pixels per edge)")
+        except (FileNotFoundError, ValueError) as exc:
+            results[name] = str(exc)
+            continue
+        bucket = buckets.setdefault(gt.shape, ([], [], []))
+        for lst, v in zip(bucket, (name, gt, pred)):
+            lst.append(v)
+        if len(bucket[0]) >= args.batch_size:
+            flush(gt.shape)
+    for shape in list(buckets):
+        flush(shape)
+
+    names = [p[0] for p in pairs]
+    images = {name: results[name] for name in names if not isinstance(results[name], str)}
+    skipped = [{"image": name, "reason": results[name]} for name in names if isinstance(results[name], str)]
+    all_metrics = [v["metrics"] for v in images.values()]
+    return {"arguments": {k: (str(v) if isinstance(v, Path) else v) for k, v in sorted(vars(args).items())},
+            "images_processed": len(images), "images": images, "aggregates": M.aggregate(all_metrics),
+            "thresholds": [{"name": n_, "count": c, "percentage": p} for n_, c, p in M.threshold_counts(all_metrics)],
+            "skipped": skipped, "unpaired": unpaired}
+
+
+def write_report(report: dict, out_dir: Path, plot: bool) -> list:
+    from .utils import compare_metrics as M
+    out_dir.mkdir(parents=True, exist_ok=True)
+    written = [out_dir / "_metrics.csv", out_dir / "_dimensions.csv", out_dir / "compare_metrics.json"]
+    thresholds = [(t["name"], t["count"], t["percentage"]) for t in report["thresholds"]]
+    M.write_csv(written[0], M.METRICS_CSV_COLUMNS, M.metrics_csv_rows(report["aggregates"], thresholds, report["images_processed"]))
+    M.write_csv(written[1], M.DIMENSION_COLUMNS, [dict(v["dimensions"], **{"Image Path": name}) for name, v in report["images"].items()])
+    with written[2].open("w", encoding="utf-8") as fh:
+        json.dump(report, fh, indent=2)
+    if plot and report["images"]:
+        written.append(out_dir / "_metrics_distribution.png")
+        M.save_distributions(written[-1], [v["metrics"] for v in report["images"].values()], report["aggregates"])
+    return written
+
+
+def main(argv=None) -> None:
+    from . import _lib
+    from .utils.cli_common import init_device_and_seed
+    _lib.refuse_wrong_result_env("compare_images.py")
+    args = parse_args(argv)
+    for key in ("gt_dir", "pred_dir", "results_dir", "output_dir"):
+        if getattr(args, key) is not None:
+            setattr(args, key, getattr(args, key).expanduser().resolve())
+    if args.output_dir is None:
+        args.output_dir = (args.results_dir if args.results_dir is not None else args.gt_dir) / "compare"
+    list_pairs(args)                                   # a missing folder is reported before the device is touched
+    device = init_device_and_seed(None)
+    report = run(args, device)
+    written = write_report(report, args.output_dir, plot=not args.no_plot)
+    for side, label in (("gt_only", "ground truth"), ("pred_only", "prediction")):
+        for name in report["unpaired"][side]:
+            print(f"Unpaired: {name} is in the {label} folder only")
+    for s in report["skipped"]:
+        print(f"Skipping {s['image']}: {s['reason']}")
+    print(f"{report['images_processed']} pair(s) compared, {len(report['skipped'])} skipped")
+    for key in ("Dice Coefficient", "IoU", "Height Metric", "Width Metric Middle"):
+        a = report["aggregates"].get(key)
+        if a and a["n"]:
+            print(f"   {key}: {a['mean']:.4f} (worst {a['worst']:.4f}, n = {a['n']})")
+    for path in written:
+        print(f"   written: {path}")
+
+
+if __name__ == "__main__":
+    main()

@@ -1226,6 +1226,60 @@ def mask_geometry(src, offsets, hw, *, elem, max_h, sample_rows, bottom_offsets,
     return bbox, bbox_widths, bottom_widths
 
 
+# ---- shape comparison of image pairs (csrc/mask_compare.hip; include/pti_vae.h "shape comparison") ------------------------
+MASK_COMPARE_MAX_EDGE = 1024                            # PTI_MASK_COMPARE_MAX_EDGE: the kernel's bound on h and w
+MASK_COMPARE_COLUMNS = L.MASK_COMPARE_COLUMNS              # the int32 columns, in order
+MASK_COMPARE_SUMS = ("sq_err_sum", "max_gt", "max_pred")
+
+
+def mask_compare(gt, pred, *, threshold=0.2, out=None):
+    """Foreground masks, largest component, hole fill and the shape numbers of a batch of image pairs in one launch
+    (``pti_mask_compare``) -> ``(counts, sums)`` device tensors.
+
+    ``gt`` / ``pred``: contiguous fp32 device images ``[n, h, w]`` or ``[n, 1, h, w]`` of one shape, finite, ``1 <= h, w <=
+    MASK_COMPARE_MAX_EDGE``.  Masks: ``gt != 0`` and ``|pred| > threshold``; the prediction's mask is cleaned to its largest
+    8-connected component (pixel count; ties go to the smallest row-major index) with its holes filled.  ``counts``: int32
+    ``[n, 24]`` in ``MASK_COMPARE_COLUMNS`` order; ``sums``: float64 ``[n, 3]`` in ``MASK_COMPARE_SUMS`` order (include/pti_vae.h
+    has the definitions).  ``counts[:, 23]`` (``status``) is 0 unless the kernel's bounded label loops overran -- it travels
+    with the results, ``utils.compare_metrics.pair_metrics`` raises on it.  ``out=(counts, sums)`` are written in place.
+    Runs on the current stream, no host sync; bitwise reproducible; the scratch buffer is cached per (stream, shape)."""
+    who = "mask_compare"
+    for name, t in (("gt", gt), ("pred", pred)):
+        if not isinstance(t, torch.Tensor) or t.dtype != F32:
+            raise TypeError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    for name, t in (("gt", gt), ("pred", pred)):
+        if not t.is_cuda or t.device != gt.device:
+            raise ValueError(f"{who}: {name} must be a CUDA(HIP) tensor on the device of gt")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+    if gt.dim() == 4 and gt.shape[1] == 1:
+        gt = gt[:, 0]
+    if pred.dim() == 4 and pred.shape[1] == 1:
+        pred = pred[:, 0]
+    if gt.dim() != 3 or pred.shape != gt.shape:
+        raise ValueError(f"{who}: expected [n, h, w] or [n, 1, h, w] images of one shape, got {tuple(gt.shape)} / {tuple(pred.shape)}")
+    n, h, w = gt.shape
+    if n < 1 or not (1 <= h <= MASK_COMPARE_MAX_EDGE and 1 <= w <= MASK_COMPARE_MAX_EDGE):
+        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)} (n >= 1, 1 <= h, w <= {MASK_COMPARE_MAX_EDGE})")
+    threshold = float(threshold)
+    if not threshold >= 0.0:
+        raise ValueError(f"{who}: threshold must be >= 0, got {threshold}")
+    if out is None:
+        out = (None, None)
+    elif len(out) != 2:
+        raise ValueError(f"{who}: out must be (counts, sums)")
+    counts = _out(out[0], (n, len(MASK_COMPARE_COLUMNS)), torch.int32, gt.device, f"{who}: out[0] (counts)")
+    sums = _out(out[1], (n, len(MASK_COMPARE_SUMS)), torch.float64, gt.device, f"{who}: out[1] (sums)")
+    nbytes = L.lib().pti_mask_compare_ws_bytes(n, h, w)
+    if nbytes <= 0:
+        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)}")
+    stream = _stream()
+    ws = _scratch("mask_compare", (n, h, w), (nbytes + 3) // 4, gt.device, stream)
+    L.check(L.lib().pti_mask_compare(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(counts), _ptr(sums), _ptr(ws),
+                                     ws.numel() * 4, stream), "pti_mask_compare")
+    return counts, sums
+
+
 # ---- display normalisation (csrc/display.hip; include/pti_vae.h "display normalisation") --------------------------------
 DISPLAY_MAX_EDGE, DISPLAY_MAX_PLANES = 4096, 65535   # the bounds of pti_display_planes
 

@@ -1,0 +1,203 @@
+"""Host arithmetic of the image-comparison report (reference src/pti_ldm_vae/analysis/metrics.py: ``ImageComparison``):
+from the integer table and the three fp64 sums of ``ops.mask_compare`` to the per-pair metrics, their aggregates with the
+reference's five outlier counts, the twelve threshold counts and the rows of its two CSV files.  No torch, fp64 throughout.
+
+What is not here: SSIM, the VGG16 cosine similarity and Euclidean distance, and the straighten / align step that the
+reference runs before measuring."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from .._lib import MASK_COMPARE_COLUMNS as COLUMNS
+
+METRIC_KEYS = ("MSE", "PSNR", "Dice Coefficient", "Dice Loss", "IoU", "Height Metric", "Width Metric Upper",
+               "Width Metric Middle", "Width Metric Lower", "Absolute Height Difference", "Absolute Width Upper Difference",
+               "Absolute Width Middle Difference", "Absolute Width Lower Difference")
+# higher is better (metrics.py:465-475); for every other key the worst value is the largest
+HIGHER_IS_BETTER = frozenset(("PSNR", "Dice Coefficient", "Height Metric", "Width Metric Upper", "Width Metric Middle",
+                              "Width Metric Lower", "IoU"))
+OUTLIER_KEYS = ("outside_1_ci", "outside_2_ci", "outside_3_ci", "outside_iqr", "outside_z")
+DIMENSION_COLUMNS = ("Image Path", "GT Height", "GT Width Upper", "GT Width Middle", "GT Width Lower", "Gen Height",
+                     "Gen Width Upper", "Gen Width Middle", "Gen Width Lower")
+METRICS_CSV_COLUMNS = ("Metric", "Average", "Worst Value", "Confidence Interval Lower (95%)", "Confidence Interval Upper (95%)",
+                       "Number of Images Processed", "Outside 1 CI", "Outside 2 CI", "Outside 3 CI", "IQR Outliers",
+                       "Z-Score Outliers", "Count", "Percentage")
+NO_GT = "no foreground component in the ground truth"
+NO_PRED = "no foreground component in the prediction"
+SMOOTH = 1e-6
+
+
+def _ratio(a: int, b: int):
+    """min / max, ``None`` when the larger term is 0 (the reference divides by zero there)."""
+    hi = max(a, b)
+    return None if hi == 0 else min(a, b) / hi
+
+
+def dimensions(row) -> dict:
+    """One row of the integer table -> the eight measured sizes under the names of ``_dimensions.csv``."""
+    c = dict(zip(COLUMNS, (int(v) for v in row)))
+    return {"GT Height": c["gt_h"], "GT Width Upper": c["gt_width_upper"], "GT Width Middle": c["gt_width_middle"],
+            "GT Width Lower": c["gt_width_lower"], "Gen Height": c["pred_h"], "Gen Width Upper": c["pred_width_upper"],
+            "Gen Width Middle": c["pred_width_middle"], "Gen Width Lower": c["pred_width_lower"]}
+
+
+def pair_metrics(counts, sums, h: int, w: int) -> list:
+    """Per image either the metric dictionary (``METRIC_KEYS`` in order) or, for a pair that is skipped, the reason as a
+    string: a side without any foreground component has no box to measure (the reference's ``except`` drops such a pair).
+
+    ``counts`` int ``[n, 24]`` / ``sums`` float64 ``[n, 3]`` as ``ops.mask_compare`` returns them (host arrays), ``h, w`` the
+    image size.  PSNR is ``inf`` at MSE 0 and ``None`` when neither image has a positive pixel; a ratio is ``None`` when
+    its larger term is 0.  A non-zero status column raises: the kernel reported an overrun of its bounded loops."""
+    counts = np.asarray(counts).reshape(-1, len(COLUMNS))
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1, 3)
+    if len(counts) != len(sums):
+        raise ValueError(f"pair_metrics: {len(counts)} count rows but {len(sums)} sum rows")
+    npix = int(h) * int(w)
+    if npix < 1:
+        raise ValueError(f"pair_metrics: bad image size {h} x {w}")
+    out = []
+    for i, (row, (sq, max_gt, max_pred)) in enumerate(zip(counts, sums)):
+        c = dict(zip(COLUMNS, (int(v) for v in row)))
+        if c["status"] != 0:
+            raise RuntimeError(f"pair_metrics: image {i}: mask_compare reported status {c['status']} (label loop overrun)")
+        if c["kept_gt"] == 0 or c["kept_pred"] == 0:
+            out.append(NO_GT if c["kept_gt"] == 0 else NO_PRED)
+            continue
+        mse = float(sq) / npix
+        peak = max(float(max_gt), float(max_pred))
+        psnr = math.inf if mse == 0 else (None if peak <= 0 else 20.0 * math.log10(peak / math.sqrt(mse)))
+        dice = (2.0 * c["intersection"] + SMOOTH) / (c["filled_pred"] + c["n_gt"] + SMOOTH)
+        d = dimensions(row)
+        m = {"MSE": mse, "PSNR": psnr, "Dice Coefficient": dice, "Dice Loss": 1.0 - dice,
+             "IoU": 1.0 if c["union"] == 0 else c["intersection"] / c["union"],
+             "Height Metric": _ratio(d["GT Height"], d["Gen Height"]),
+             "Width Metric Upper": _ratio(d["GT Width Upper"], d["Gen Width Upper"]),
+             "Width Metric Middle": _ratio(d["GT Width Middle"], d["Gen Width Middle"]),
+             "Width Metric Lower": _ratio(d["GT Width Lower"], d["Gen Width Lower"]),
+             "Absolute Height Difference": abs(d["GT Height"] - d["Gen Height"]),
+             "Absolute Width Upper Difference": abs(d["GT Width Upper"] - d["Gen Width Upper"]),
+             "Absolute Width Middle Difference": abs(d["GT Width Middle"] - d["Gen Width Middle"]),
+             "Absolute Width Lower Difference": abs(d["GT Width Lower"] - d["Gen Width Lower"])}
+        assert tuple(m) == METRIC_KEYS
+        out.append(m)
+    return out
+
+
+def aggregate(all_metrics: list) -> dict:
+    """key -> ``{n, none, mean, std, ci95, worst, outliers}`` over a list of metric dictionaries.
+
+    ``None`` entries are left out of a key's statistics and counted in ``none``; ``n`` is what is left.  ``std`` is the
+    population value, ``ci95 = mean -+ 1.96 std / sqrt(n)``, ``worst`` the smallest value of a ``HIGHER_IS_BETTER`` key and
+    the largest of any other, ``outliers`` the five counts of the reference's ``count_outliers``: outside 1 / 2 / 3 half-widths
+    of the confidence interval round the mean, outside the 1.5 IQR fences, ``|z| > 3`` (0 when ``std`` is 0).  A key without
+    any value has ``None`` statistics and zero counts."""
+    keys = list(all_metrics[0]) if all_metrics else []
+    out = {}
+    for key in keys:
+        data = np.array([m[key] for m in all_metrics if m[key] is not None], dtype=np.float64)
+        n, none = len(data), len(all_metrics) - len(data)
+        if n == 0:
+            out[key] = {"n": 0, "none": none, "mean": None, "std": None, "ci95": None, "worst": None,
+                        "outliers": dict.fromkeys(OUTLIER_KEYS, 0)}
+            continue
+        with np.errstate(invalid="ignore"):
+            mean, std = float(np.mean(data)), float(np.std(data))
+            half = 1.96 * (std / math.sqrt(n))
+            lo, hi = mean - half, mean + half
+            margin = (hi - lo) / 2
+            q1, q3 = np.percentile(data, [25, 75])
+            iqr = q3 - q1
+            outliers = {
+                "outside_1_ci": int(np.sum((data < lo) | (data > hi))),
+                "outside_2_ci": int(np.sum((data < mean - 2 * margin) | (data > mean + 2 * margin))),
+                "outside_3_ci": int(np.sum((data < mean - 3 * margin) | (data > mean + 3 * margin))),
+                "outside_iqr": int(np.sum((data < q1 - 1.5 * iqr) | (data > q3 + 1.5 * iqr))),
+                "outside_z": 0 if std == 0 else int(np.sum(np.abs((data - mean) / std) > 3)),
+            }
+        worst = float(data.min() if key in HIGHER_IS_BETTER else data.max())
+        out[key] = {"n": n, "none": none, "mean": mean, "std": std, "ci95": [lo, hi], "worst": worst, "outliers": outliers}
+    return out
+
+
+def threshold_counts(all_metrics: list) -> list:
+    """The twelve ``(name, count, percentage)`` rows of metrics.py:770-783 over the processed pairs; a ``None`` metric passes
+    no threshold; the percentage is of all processed pairs, rounded to two places."""
+    n = len(all_metrics)
+
+    def count(key, test):
+        return sum(1 for m in all_metrics if m[key] is not None and test(m[key]))
+
+    rows = []
+    for level in (0.95, 0.97, 0.90):
+        rows.append((f"Exams with Height Metric > {level:.2f}", count("Height Metric", lambda v: v > level)))
+        rows.append((f"Exams with Width Metric > {level:.2f}", count("Width Metric Middle", lambda v: v > level)))
+    for limit in (5, 10):
+        rows.append((f"Exams with Absolute Height Difference < {limit}", count("Absolute Height Difference", lambda v: v < limit)))
+        rows.append((f"Exams with Absolute Middle Width Difference < {limit}",
+                     count("Absolute Width Middle Difference", lambda v: v < limit)))
+        rows.append((f"Exams with Absolute Lower Width Difference < {limit}",
+                     count("Absolute Width Lower Difference", lambda v: v < limit)))
+    return [(name, c, round(c / n * 100, 2) if n else 0.0) for name, c in rows]
+
+
+def metrics_csv_rows(aggregates: dict, thresholds: list, n_images: int) -> list:
+    """Rows of ``_metrics.csv`` as dictionaries over ``METRICS_CSV_COLUMNS`` (missing cells stay empty): one row per metric
+    with its rounded statistics, then the threshold rows with ``Count`` and ``Percentage``."""
+    rows = []
+    r3 = lambda v: "" if v is None else round(v, 3)   # noqa: E731
+    for key, a in aggregates.items():
+        ci = a["ci95"] or (None, None)
+        rows.append({"Metric": key, "Average": r3(a["mean"]), "Worst Value": r3(a["worst"]),
+                     "Confidence Interval Lower (95%)": r3(ci[0]), "Confidence Interval Upper (95%)": r3(ci[1]),
+                     "Number of Images Processed": n_images, "Outside 1 CI": a["outliers"]["outside_1_ci"],
+                     "Outside 2 CI": a["outliers"]["outside_2_ci"], "Outside 3 CI": a["outliers"]["outside_3_ci"],
+                     "IQR Outliers": a["outliers"]["outside_iqr"], "Z-Score Outliers": a["outliers"]["outside_z"]})
+    for name, c, pct in thresholds:
+        rows.append({"Metric": name, "Count": c, "Percentage": pct})
+    return rows
+
+
+def write_csv(path, columns, rows) -> None:
+    """``;``-separated file with a header line; ``rows`` are dictionaries, a missing cell is left empty."""
+    import csv
+    with open(path, "w", newline="", encoding="utf-8") as fh:
+        writer = csv.DictWriter(fh, fieldnames=list(columns), delimiter=";", restval="")
+        writer.writeheader()
+        writer.writerows(rows)
+
+
+def save_distributions(path, all_metrics: list, aggregates: dict) -> None:
+    """One histogram per key with the mean (dashed), the IQR fences and the +-3 sigma lines, as the reference's
+    ``plot_metric_distributions_with_ci`` draws them; written to ``path``, never shown."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    keys = [k for k, a in aggregates.items() if a["n"] > 0]
+    cols = 3
+    rows = max((len(keys) + cols - 1) // cols, 1)
+    fig, axes = plt.subplots(rows, cols, figsize=(15, rows * 4), squeeze=False)
+    axes = axes.flatten()
+    for ax, key in zip(axes, keys):
+        data = np.array([m[key] for m in all_metrics if m[key] is not None], dtype=np.float64)
+        data = data[np.isfinite(data)]
+        a = aggregates[key]
+        if len(data):
+            ax.hist(data, bins=20, color="lightblue", edgecolor="black", alpha=0.7)
+            q1, q3 = np.percentile(data, [25, 75])
+            mean, std = float(np.mean(data)), float(np.std(data))
+            ax.axvline(mean, color="red", linestyle="--", label="Mean", lw=2)
+            ax.axvline(q1 - 1.5 * (q3 - q1), color="orange", linestyle="-", label="IQR Lower", lw=2)
+            ax.axvline(q3 + 1.5 * (q3 - q1), color="orange", linestyle="-", label="IQR Upper", lw=2)
+            ax.axvline(mean - 3 * std, color="red", linestyle="-", label="Z-Score -3", lw=2)
+            ax.axvline(mean + 3 * std, color="red", linestyle="-", label="Z-Score +3", lw=2)
+            ax.legend(loc="upper left", fontsize=8)
+        ax.set_title(f"Distribution of {key} (n = {a['n']})", fontsize=12)
+        ax.set_xlabel(f"{key} values", fontsize=10)
+        ax.set_ylabel("Frequency", fontsize=10)
+    for ax in axes[len(keys):]:
+        fig.delaxes(ax)
+    fig.tight_layout()
+    fig.savefig(path)
+    plt.close(fig)
