@@ -30,10 +30,9 @@ constexpr int FT_W = 64, FT_H = 16, FT_THREADS = 256;
 constexpr int FIELD_MAX_RADIUS = PTI_ELASTIC_MAX_RADIUS;
 constexpr int FIELD_MAX_TAPS = ((2 * FIELD_MAX_RADIUS + 1 + 3) / 4) * 4;   // 64
 
-__device__ __forceinline__ uint32_t aug_mix(uint32_t h) { return lowbias32(h); }   // pti_common.h
 // uniform in [-1, 1): the top 24 bits of the hash as a signed fraction -- exact in fp32
 __device__ __forceinline__ float aug_noise(uint32_t k0, uint32_t k1c, uint32_t i) {
-  const uint32_t h = aug_mix(aug_mix(i + k0) ^ k1c);
+  const uint32_t h = lowbias32(lowbias32(i + k0) ^ k1c);
   return (float)((int)(h >> 8) - 8388608) * (1.0f / 8388608.0f);
 }
 __device__ __forceinline__ int reflect(int i, int n) { return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i); }

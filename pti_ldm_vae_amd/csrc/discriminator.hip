@@ -19,8 +19,6 @@
 
 namespace {
 
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 // ---- patches of the 1-channel fp32 image: [n][h/2][w/2][32] bf16 = 16 taps (ky*4+kx) + 16 zero columns ------------
 __global__ __launch_bounds__(256) void pd_im2col_image_kernel(const float* __restrict__ img, bf16* __restrict__ P, int N,
                                                               int H, int W) {

@@ -70,12 +70,6 @@ __global__ __launch_bounds__(DT_TILE) void tied_ranks_kernel(const float* __rest
   if (i < n) rank2[(long long)blockIdx.y * n + i] = n + 1 + acc - pad;
 }
 
-__device__ __forceinline__ unsigned long long dt_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(DT_TILE) void rank_moments_kernel(const int* __restrict__ rank2, int n, int m,
                                                                long long* __restrict__ sums, long long* __restrict__ gram) {
   __shared__ unsigned long long s_red[DT_TILE / 64][2];
@@ -90,8 +84,8 @@ __global__ __launch_bounds__(DT_TILE) void rank_moments_kernel(const int* __rest
     dot += (unsigned long long)va * vb;   // one 32 x 32 -> 64-bit multiply-add
     sum += va;
   }
-  dot = dt_wave_sum(dot);
-  sum = dt_wave_sum(sum);
+  dot = wave_sum(dot);
+  sum = wave_sum(sum);
   if (lane == 0) {
     s_red[wave][0] = dot;
     s_red[wave][1] = sum;

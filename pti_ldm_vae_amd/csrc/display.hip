@@ -137,8 +137,7 @@ __global__ __launch_bounds__(DP_THREADS) void display_planes_kernel(DpArgs g) {
       if (wave == 0) {
         const u32x4 c = *(const u32x4*)&hist[0][4 * lane];
         uint32_t t = c[0] + c[1] + c[2] + c[3];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        t = wave_sum(t);
         if (lane == 0) {
           s_n = t;
           for (int q = 0; q < 2; ++q) {

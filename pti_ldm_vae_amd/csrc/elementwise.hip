@@ -499,7 +499,9 @@ struct ArArgs {
   float gamma;
 };
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {   // fixed order: wave shuffles, then 4 partials
+// sum over a 256-thread workgroup; under -ffast-math the pairs below compile to the chain ((w0 + w1) + w2) + w3 at both
+// call sites: not block_sum<4>, whose order differs from one call site to the next (pti_common.h)
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
   v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;

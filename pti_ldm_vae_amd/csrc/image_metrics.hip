@@ -47,12 +47,6 @@ struct ImArgs {
   ImTaps taps;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(IM_THREADS) void image_metrics_tile_kernel(ImArgs a) {
   __shared__ float sx[IM_ST * IM_ST];
   __shared__ float sy[IM_ST * IM_ST];
@@ -146,7 +140,7 @@ __global__ __launch_bounds__(IM_THREADS) void image_metrics_tile_kernel(ImArgs a
   }
 
   // ---- tile reduction, fp64, fixed order: shuffles inside the wave, waves 0..3 in order ----
-  const double w_sq = wave_sum_f64((double)s_sq), w_ab = wave_sum_f64((double)s_ab), w_ss = wave_sum_f64((double)s_ss);
+  const double w_sq = wave_sum((double)s_sq), w_ab = wave_sum((double)s_ab), w_ss = wave_sum((double)s_ss);
   if ((tid & 63) == 0) {
     red[tid >> 6][0] = w_sq;
     red[tid >> 6][1] = w_ab;
@@ -172,9 +166,9 @@ __global__ __launch_bounds__(64) void image_metrics_finalize_kernel(const float*
     s1 += (double)p[3 * r + 1];
     s2 += (double)p[3 * r + 2];
   }
-  s0 = wave_sum_f64(s0);
-  s1 = wave_sum_f64(s1);
-  s2 = wave_sum_f64(s2);
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
   if (lane == 0) {
     const double mse = s0 * inv_count;
     float* o = out_n4 + 4 * (long long)n;

@@ -52,12 +52,6 @@ __device__ __forceinline__ float lp_sqrt(float x) { return __builtin_amdgcn_sqrt
 
 __device__ __forceinline__ int lp_tiles_of(int n) { return (n + LP_TILE - 1) / LP_TILE; }
 
-__device__ __forceinline__ double lp_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // four consecutive columns k .. k+3 of `row` of p, minus the centre; zeros for a row >= n or a column >= d
 __device__ __forceinline__ f32x4 lp_fetch(const float* __restrict__ p, long long ld, int n, int row, int k,
                                           const float* __restrict__ center, int d, int vec) {
@@ -254,20 +248,6 @@ __device__ __forceinline__ void gs_col_stats(const float* __restrict__ p, long l
   sd = cnt > 1 ? lp_sqrt(__fdiv_rn(ss, (float)cnt)) : 0.f;
 }
 
-// fixed-order sum of one double per thread over the workgroup (wave shuffles, then waves 0..3 in order), returned to
-// every thread
-__device__ __forceinline__ double gs_block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  const double w = lp_wave_sum_f64(v);
-  __syncthreads();                       // `red` may still be read from an earlier call
-  if ((tid & 63) == 0) red[tid >> 6] = w;
-  __syncthreads();
-  double t = red[0];
-#pragma unroll
-  for (int wv = 1; wv < LP_THREADS / 64; ++wv) t += red[wv];
-  return t;
-}
-
 __global__ __launch_bounds__(GS_COLS) void latent_group_cols_kernel(GsArgs g) {
   __shared__ double red[GS_COLS / 64];
   const int e = blockIdx.y, chunk = blockIdx.x;
@@ -286,9 +266,9 @@ __global__ __launch_bounds__(GS_COLS) void latent_group_cols_kernel(GsArgs g) {
     v1 = sa;
     v2 = sb;
   }
-  const double s0 = gs_block_sum((double)v0, red);
-  const double s1 = gs_block_sum((double)v1, red);
-  const double s2 = gs_block_sum((double)v2, red);
+  const double s0 = block_sum<GS_COLS / 64>((double)v0, red);
+  const double s1 = block_sum<GS_COLS / 64>((double)v1, red);
+  const double s2 = block_sum<GS_COLS / 64>((double)v2, red);
   if (threadIdx.x == 0) {
     double* dst = g.cols + ((long long)e * g.chunks + chunk) * 3;
     dst[0] = s0;
@@ -331,7 +311,7 @@ __global__ __launch_bounds__(LP_THREADS) void latent_group_cross_kernel(GsArgs g
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (row0 + ty * 4 + i < na && col0 + tx * 4 + j < nb) s += (double)lp_sqrt(tot[i][j]);
-    const double sum = gs_block_sum(s, red);
+    const double sum = block_sum<LP_THREADS / 64>(s, red);
     if (threadIdx.x == 0) g.cross[(long long)e * g.tiles_max + t] = sum;
     __syncthreads();                     // the staging buffers are rewritten by the next tile
   }
@@ -358,10 +338,10 @@ __global__ __launch_bounds__(64) void latent_group_finalize_kernel(GsArgs g, flo
   const int tiles = min(lp_tiles_of(na) * lp_tiles_of(nb), g.tiles_max);
   const double* px = g.cross + (long long)e * g.tiles_max;
   for (int t = lane; t < tiles; t += 64) s3 += px[t];
-  s0 = lp_wave_sum_f64(s0);
-  s1 = lp_wave_sum_f64(s1);
-  s2 = lp_wave_sum_f64(s2);
-  s3 = lp_wave_sum_f64(s3);
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  s3 = wave_sum(s3);
   if (lane == 0) {
     o[0] = (float)sqrt(s0);
     o[1] = (float)(s1 / (double)g.o.d);

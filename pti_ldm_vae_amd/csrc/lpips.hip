@@ -92,8 +92,7 @@ __global__ __launch_bounds__(256) void lpips_tap_fwd_kernel(const float* __restr
   if (tid < 64) {
     float v = 0.f;
     for (int i = tid; i < PIX; i += 64) v += red[0][i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum(v);
     if (tid == 0) part[(size_t)n * gridDim.x + blockIdx.x] = v;
   }
 }

@@ -66,22 +66,6 @@ __device__ __forceinline__ bool mc_failed(const McShared& S) {
   return e != 0;
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // The two masks.  Ordinary float compares on the loaded values: the library is built with -ffast-math, but also with
 // -fno-finite-math-only (so a compare is not folded on the assumption that no NaN or infinity exists) and without
 // flush-to-zero of fp32 denormals (gfx9 keeps them, and v_cmp honours the mode), and the operands are the loaded words and
@@ -136,7 +120,7 @@ __device__ bool mc_label(const float* img, float thr, int h, int w, int* L, int*
     mc_st(cnt + p, 0);
     nfg += f;
   }
-  nfg = wave_sum_i(nfg);
+  nfg = wave_sum(nfg);
   if (lane == 0 && nfg) atomicAdd(&S.nfg[SIDE], nfg);
   mc_phase();
 
@@ -180,7 +164,7 @@ __device__ bool mc_label(const float* img, float thr, int h, int w, int* L, int*
       if (f && r != r0) atomicAdd(cnt + r, 1);
     }
   }
-  ncomp = wave_sum_i(ncomp);
+  ncomp = wave_sum(ncomp);
   if (lane == 0 && ncomp) atomicAdd(&S.ncomp[SIDE], ncomp);
   if (mc_failed(S)) return false;
 
@@ -208,7 +192,7 @@ __device__ bool mc_label(const float* img, float thr, int h, int w, int* L, int*
       x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
     }
   }
-  x0 = wave_min_i(x0); y0 = wave_min_i(y0); x1 = wave_max_i(x1); y1 = wave_max_i(y1);
+  x0 = wave_min(x0); y0 = wave_min(y0); x1 = wave_max(x1); y1 = wave_max(y1);
   if (lane == 0 && x1 >= 0) {
     atomicMin(&S.box[SIDE][0], x0); atomicMin(&S.box[SIDE][1], y0);
     atomicMax(&S.box[SIDE][2], x1); atomicMax(&S.box[SIDE][3], y1);
@@ -311,9 +295,9 @@ __global__ __launch_bounds__(MC_THREADS) void mask_compare_kernel(McArgs a) {
       mp = rp > mp ? rp : mp;
     }
   }
-  np = wave_sum_i(np); inter = wave_sum_i(inter);
-  gw0 = wave_sum_i(gw0); gw1 = wave_sum_i(gw1); gw2 = wave_sum_i(gw2);
-  rw0 = wave_sum_i(rw0); rw1 = wave_sum_i(rw1); rw2 = wave_sum_i(rw2);
+  np = wave_sum(np); inter = wave_sum(inter);
+  gw0 = wave_sum(gw0); gw1 = wave_sum(gw1); gw2 = wave_sum(gw2);
+  rw0 = wave_sum(rw0); rw1 = wave_sum(rw1); rw2 = wave_sum(rw2);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     sq += __shfl_xor(sq, o, 64);

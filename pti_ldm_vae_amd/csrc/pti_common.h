@@ -219,10 +219,48 @@ __device__ __forceinline__ uint32_t lowbias32(uint32_t h) {
   return h;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// ---- wave and workgroup reductions ----------------------------------------------------------------------
+// xor butterfly 32, 16, ... 1 over the 64 lanes: the result, the same bits, in every lane
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// sum of one value per thread over a workgroup of WAVES waves, returned to every thread; `red` holds WAVES elements.
+// The order in which the partials w0 .. w3 of the waves are added is the compiler's, not this loop's: the library is
+// built with -ffast-math, which lets it re-associate a floating-point sum.  In the device assembly of the gfx950 build
+// every call of block_sum<4> is one of two chains, fixed per call site and the same in every thread and every run:
+//   ((w0 + w1) + w2) + w3   latent_group_cols_kernel's first two sums, regression_metrics_kernel's loss and |d| sums
+//   ((w2 + w3) + w1) + w0   latent_group_cols_kernel's third sum, latent_group_cross_kernel, regression_metrics_kernel's
+//                           d^2 sum
+// The order is not pinned (#pragma clang fp reassociate(off) would make all of them the first chain): that changes
+// the code of the second group, and with it bits that committed goldens hold.  After a change to a caller, or a new
+// one, read the order from the assembly; integer sums have no order.
+template <int WAVES, class T>
+__device__ __forceinline__ T block_sum(T v, T* red) {
+  const int tid = threadIdx.x;
+  const T w = wave_sum(v);
+  __syncthreads();                       // `red` may still be read from an earlier call
+  if ((tid & 63) == 0) red[tid >> 6] = w;
+  __syncthreads();
+  T t = red[0];
+#pragma unroll
+  for (int wv = 1; wv < WAVES; ++wv) t += red[wv];
+  return t;
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -45,17 +45,6 @@ struct RaArgs {
 
 __device__ __forceinline__ unsigned ra_code(float vj, float vi) { return (vj > vi ? 1u : 0u) | (vj < vi ? RA_DOWN : 0u); }
 
-__device__ __forceinline__ int ra_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double ra_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // LP: the channel count rounded up to a multiple of 4; the padding channels are zeros on both sides (Z = 0)
 template <int LP>
 __global__ __launch_bounds__(RA_TILE) void rank_agreement_tile_kernel(RaArgs g) {
@@ -141,8 +130,8 @@ __global__ __launch_bounds__(RA_TILE) void rank_agreement_tile_kernel(RaArgs g) 
 #pragma unroll
     for (int c = 0; c <= LP; ++c) {
       const unsigned v = acc[k][c];
-      const int conc = ra_wave_sum((int)((v & (RA_DOWN - 1u)) + (v >> 22)));
-      const int disc = ra_wave_sum((int)((v >> 11) & (RA_DOWN - 1u)));
+      const int conc = wave_sum((int)((v & (RA_DOWN - 1u)) + (v >> 22)));
+      const int disc = wave_sum((int)((v >> 11) & (RA_DOWN - 1u)));
       if (lane == 0) {
         s_red[wave][(k * (LP + 1) + c) * 2] = conc;
         s_red[wave][(k * (LP + 1) + c) * 2 + 1] = disc;
@@ -150,7 +139,7 @@ __global__ __launch_bounds__(RA_TILE) void rank_agreement_tile_kernel(RaArgs g) 
     }
 #pragma unroll
   for (int k = 0; k < RA_QB; ++k) {
-    const double t = ra_wave_sum(lacc[k]);
+    const double t = wave_sum(lacc[k]);
     if (lane == 0) s_loss[wave][k] = t;
   }
   __syncthreads();

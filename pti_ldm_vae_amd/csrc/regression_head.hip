@@ -85,19 +85,6 @@ __device__ __forceinline__ float mh_act(float v, int act) {
   }
 }
 
-__device__ __forceinline__ float mh_wave_sum(float v) {
-#pragma clang fp reassociate(off)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double mh_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // grid (row tiles, unit blocks, split ? slabs : 1)
 __global__ __launch_bounds__(MH_THREADS) void mlp_head_first_kernel(MhFirst p) {
 #pragma clang fp reassociate(off)
@@ -217,7 +204,7 @@ __global__ __launch_bounds__(MH_THREADS) void mlp_head_tail_kernel(MhTail p) {
         for (int r = 0; r < MH_TR; ++r) part[r] = fmaf(buf[cur][r][k], wv, part[r]);
       }
 #pragma unroll
-      for (int r = 0; r < MH_TR; ++r) part[r] = mh_wave_sum(part[r]);
+      for (int r = 0; r < MH_TR; ++r) part[r] = wave_sum(part[r]);
       if (lane == 0) {
         const float b = bias[j];
 #pragma unroll
@@ -262,19 +249,6 @@ __global__ __launch_bounds__(MH_THREADS) void mlp_head_tail_kernel(MhTail p) {
   }
 }
 
-// fixed-order sum of one double per thread over the workgroup (wave shuffles, then waves 0..3 in order), to every thread
-__device__ __forceinline__ double mh_block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  const double w = mh_wave_sum_f64(v);
-  __syncthreads();                       // `red` may still be read from an earlier call
-  if ((tid & 63) == 0) red[tid >> 6] = w;
-  __syncthreads();
-  double t = red[0];
-#pragma unroll
-  for (int wv = 1; wv < MH_THREADS / 64; ++wv) t += red[wv];
-  return t;
-}
-
 // one workgroup; out[0] = mean over the chunks of `batch` rows of (sum rowloss / (rows * T)); out[1..T] MAE, out[T+1..2T] MSE
 // per target; out[2T+1], out[2T+2] their means over the targets
 __global__ __launch_bounds__(MH_THREADS) void regression_metrics_kernel(const float* __restrict__ pred,
@@ -293,7 +267,7 @@ __global__ __launch_bounds__(MH_THREADS) void regression_metrics_kernel(const fl
     for (int r = 0; r < rows; ++r) s += (double)rowloss[lo + r];
     v += s / ((double)rows * (double)t);
   }
-  const double loss = mh_block_sum(v, red) / (double)chunks;
+  const double loss = block_sum<MH_THREADS / 64>(v, red) / (double)chunks;
   for (int k = 0; k < t; ++k) {
     double sa = 0.0, sq = 0.0;
     for (int r = tid; r < n; r += MH_THREADS) {
@@ -301,8 +275,8 @@ __global__ __launch_bounds__(MH_THREADS) void regression_metrics_kernel(const fl
       sa += fabs(df);
       sq += df * df;
     }
-    sa = mh_block_sum(sa, red);
-    sq = mh_block_sum(sq, red);
+    sa = block_sum<MH_THREADS / 64>(sa, red);
+    sq = block_sum<MH_THREADS / 64>(sq, red);
     if (tid == 0) {
       per_target[k] = sa / (double)n;
       per_target[t + k] = sq / (double)n;

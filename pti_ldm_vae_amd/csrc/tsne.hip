@@ -51,16 +51,11 @@ constexpr int TS_WAVES = 4096;       // wavefronts the force pass aims at
 constexpr int TS_UPD_ROWS = 64;      // rows of one workgroup of the update
 constexpr float TS_EPS = 2.220446e-16f;
 
-__device__ __forceinline__ double ts_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// fixed-order sums of two doubles per thread over a 256-thread workgroup, returned to every thread
+// fixed-order sums of two doubles per thread over a 256-thread workgroup, returned to every thread; not two
+// block_sum<4> calls: both values share one pair of barriers
 __device__ __forceinline__ void ts_block_sum2(double& a, double& b, double* red) {
   const int tid = threadIdx.x;
-  const double wa = ts_wave_sum(a), wb = ts_wave_sum(b);
+  const double wa = wave_sum(a), wb = wave_sum(b);
   __syncthreads();                       // `red` may still be read from an earlier call
   if ((tid & 63) == 0) {
     red[tid >> 6] = wa;
@@ -297,9 +292,9 @@ __global__ __launch_bounds__(64) void tsne_forces_kernel(TsStep a) {
   for (int r = 0; r < TS_ROWS; ++r) {
     double f[5];
 #pragma unroll
-    for (int v = 0; v < 5; ++v) f[v] = ts_wave_sum((double)acc[r][v]);
+    for (int v = 0; v < 5; ++v) f[v] = wave_sum((double)acc[r][v]);
     bs_num += f[0];
-    if (KL) bs_pl += ts_wave_sum(pl[r]);
+    if (KL) bs_pl += wave_sum(pl[r]);
     if (lane == 0 && row0 + r < n) {
       double* dst = a.rowpart + ((long long)chunk * n + row0 + r) * 4;
       dst[0] = f[1];
@@ -355,7 +350,7 @@ __global__ __launch_bounds__(TS_THREADS) void tsne_update_kernel(TsStep a, int w
         gn += (double)gg * (double)gg;
       }
     }
-    gn = ts_wave_sum(gn);
+    gn = wave_sum(gn);
     if (tid == 0) a.gradpart[blockIdx.x] = gn;
   }
   if (with_record && blockIdx.x == 0 && tid == 0) {
@@ -368,7 +363,7 @@ __global__ __launch_bounds__(64) void tsne_norm_kernel(const double* __restrict_
                                                        double* __restrict__ record) {
   double s = 0.0;
   for (int t = threadIdx.x; t < count; t += 64) s += gradpart[t];
-  s = ts_wave_sum(s);
+  s = wave_sum(s);
   if (threadIdx.x == 0) record[1] = sqrt(s);
 }
 

@@ -53,16 +53,11 @@ constexpr int UM_TILE = 32;
 
 typedef unsigned long long um_key;
 
-__device__ __forceinline__ double um_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// fixed-order sum over a 256-thread workgroup, returned to every thread
+// sum over a 256-thread workgroup, to every thread; compiles to ((w0 + w1) + w2) + w3 as written: not block_sum<4>, whose
+// loop compiles to another order of these adds here (pti_common.h)
 __device__ __forceinline__ double um_block_sum(double v, double* red) {
   const int tid = threadIdx.x;
-  const double w = um_wave_sum(v);
+  const double w = wave_sum(v);
   __syncthreads();
   if ((tid & 63) == 0) red[tid >> 6] = w;
   __syncthreads();
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(UM_THREADS) void umap_rowsum_kernel(const float* __
   if (i >= n) return;                                    // wave-uniform
   double s = 0.0;
   for (int t = lane; t < k; t += 64) s += (double)knn_dist[(long long)i * k + t];
-  s = um_wave_sum(s);
+  s = wave_sum(s);
   if (lane == 0) rowsum[i] = s;
 }
 
@@ -162,7 +157,7 @@ __device__ __forceinline__ double um_sigma_search(const double* dd, int lane, in
       const int t = lane + 64 * c;
       if (t >= 1 && t < k) psum += dd[c] > 0.0 ? exp(-dd[c] / mid) : 1.0;
     }
-    psum = um_wave_sum(psum);                            // the same bits in every lane
+    psum = wave_sum(psum);                            // the same bits in every lane
     if (fabs(psum - target) < 1e-5) break;
     if (psum > target) {
       hi = mid;
@@ -191,8 +186,7 @@ __global__ __launch_bounds__(UM_THREADS) void umap_sigma_kernel(const int* __res
     d[c] = t < k ? knn_dist[(long long)i * k + t] : 0.f;
     if (d[c] > 0.f) least = fminf(least, d[c]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) least = fminf(least, __shfl_xor(least, o, 64));
+  least = wave_min(least);
   const float rho = least == INFINITY ? 0.f : least;
   double dd[UM_MAX_K / 64];
 #pragma unroll
@@ -250,8 +244,7 @@ __global__ __launch_bounds__(UM_THREADS) void umap_union_kernel(float* __restric
     }
     if (bi != bj && j0 + r < n && i0 + tx < n) w[(long long)(j0 + r) * n + i0 + tx] = um_union(ta[tx][r], tb[r][tx]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) top = fmaxf(top, __shfl_xor(top, o, 64));
+  top = wave_max(top);
   if ((tid & 63) == 0) red[tid >> 6] = top;
   __syncthreads();
   if (tid == 0) dst[0] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -262,8 +255,7 @@ __global__ __launch_bounds__(UM_THREADS) void umap_wmax_kernel(const float* __re
   __shared__ float red[UM_THREADS / 64];
   float top = 0.f;
   for (int t = threadIdx.x; t < count; t += UM_THREADS) top = fmaxf(top, partial[t]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) top = fmaxf(top, __shfl_xor(top, o, 64));
+  top = wave_max(top);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = top;
   __syncthreads();
   if (threadIdx.x == 0) wmax[0] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -290,8 +282,7 @@ __global__ __launch_bounds__(UM_THREADS) void umap_count_kernel(const float* __r
   const float top = wmax[0];
   int c = 0;
   for (int j = tid; j < n; j += UM_THREADS) c += um_kept(w[(long long)i * n + j], top, n_epochs) ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum(c);
   if ((tid & 63) == 0) red[tid >> 6] = c;
   __syncthreads();
   if (tid == 0) count[i] = red[0] + red[1] + red[2] + red[3];
@@ -395,8 +386,8 @@ __global__ __launch_bounds__(UM_THREADS) void umap_epoch_kernel(UmEpoch u) {
       }
     }
   }
-  sx = um_wave_sum(sx);
-  sy = um_wave_sum(sy);
+  sx = wave_sum(sx);
+  sy = wave_sum(sy);
   if (lane == 0) {
     u.y_out[2 * i] = (float)(yx + u.alpha * sx);
     u.y_out[2 * i + 1] = (float)(yy + u.alpha * sy);
@@ -438,11 +429,10 @@ __global__ __launch_bounds__(UM_THREADS) void umap_tsigma_kernel(const int* __re
     sx += (double)v * (double)y_train[2 * j];
     sy += (double)v * (double)y_train[2 * j + 1];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) top = fmaxf(top, __shfl_xor(top, o, 64));
-  sw = um_wave_sum(sw);
-  sx = um_wave_sum(sx);
-  sy = um_wave_sum(sy);
+  top = wave_max(top);
+  sw = wave_sum(sw);
+  sx = wave_sum(sx);
+  sy = wave_sum(sy);
   if (lane == 0) {
     sigma_out[i] = (float)sigma;
     rowmax[i] = top;
@@ -518,8 +508,8 @@ __global__ __launch_bounds__(UM_THREADS) void umap_transform_kernel(UmTransform 
         }
       }
     }
-    sx = um_wave_sum(sx);                                // the same bits in every lane
-    sy = um_wave_sum(sy);
+    sx = wave_sum(sx);                                // the same bits in every lane
+    sy = wave_sum(sy);
     const double alpha = u.initial_alpha * (1.0 - (double)epoch / (double)u.n_epochs);
     yx = (float)(px + alpha * sx);
     yy = (float)(py + alpha * sy);

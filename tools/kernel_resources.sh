@@ -2,8 +2,8 @@
 # Per-kernel VGPR / scratch / occupancy / LDS of one csrc/*.hip file, as hipcc reports them (no GPU needed).
 # usage: tools/kernel_resources.sh conv_mfma.hip
 cd "$(dirname "$0")/../pti_ldm_vae_amd/csrc"
-hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -ffast-math -fno-finite-math-only -Wno-unused-value -Wno-pass-failed \
-  -x hip -c "$1" -o /tmp/kres_$$.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
+eval "$(grep '^FLAGS=' build.sh)"   # the library's own compile flags
+hipcc $FLAGS -x hip -c "$1" -o /tmp/kres_$$.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
 import sys,re,subprocess
 cur=None;rows=[]
 for l in sys.stdin:
