@@ -761,6 +761,23 @@ int pti_joint_histogram(const float* zt, int64_t ldz, const float* attrs, int64_
                         const double* edges_z, const double* edges_a, uint8_t* bins_z, uint8_t* bins_a, int32_t* counts,
                         void* workspace, int64_t ws_bytes, pti_stream_t s);
 
+/* ---- k-nearest-neighbour mutual information: radii and range counts (csrc/ksg.hip) ----
+ * The integer part of the Kraskov-Stoegbauer-Grassberger estimator 1 as scikit-learn's _compute_mi_cc computes it, for every
+ * (attribute q, channel c).  zt fp32 [l][ldz] and attrs fp32 [na][lda] as in pti_rank_agreement, FINITE; for the pair's
+ * columns x = zt[c], y = attrs[q] and every row i:
+ *   dx_ij = |x_i - x_j|, dy_ij = |y_i - y_j|, each ONE IEEE fp32 subtraction (round to nearest, subnormals kept);
+ *   d_ij = max(dx_ij, dy_ij) for j != i -- self is left out by its index, so an exact duplicate of row i is a neighbour
+ *   at distance 0;
+ *   eps[q][c][i] = the k-th smallest d_ij, with multiplicity;         r = the largest fp32 below eps, or 0 when eps == 0;
+ *   nx[q][c][i] = #{j != i : dx_ij <= r},   ny[q][c][i] = #{j != i : dy_ij <= r}.
+ * eps fp32 [na][l][n], nx and ny int32 [na][l][n], dense.  Every cell is one of the distances or a count: independent of
+ * the order of evaluation, of row padding and of the other columns in the call; bitwise reproducible.  One launch on the
+ * caller's stream, no workspace, no atomics, no host synchronisation.  Refused before any launch: null pointers, k < 1,
+ * l or na < 1, n < k + 1, a row stride below n, a misaligned buffer (PTI_EINVAL); k > 16, n > 32768, l > 16, na > 16
+ * (PTI_EUNSUPPORTED).                                                                                                  */
+int pti_ksg_counts(const float* zt, int64_t ldz, const float* attrs, int64_t lda, int n, int l, int na, int k, float* eps,
+                   int32_t* nx, int32_t* ny, pti_stream_t s);
+
 /* ---- shape comparison of image pairs (reference src/pti_ldm_vae/analysis/metrics.py:143-209,312-398: generate_clean_mask,
  *      dice_coefficient, iou, compute_object_dimensions, calculate_psnr; csrc/mask_compare.hip) ----
  * gt, pred: fp32 [n][h][w], dense, FINITE; 1 <= n, 1 <= h, w <= PTI_MASK_COMPARE_MAX_EDGE; threshold >= 0.

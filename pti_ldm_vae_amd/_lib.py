@@ -192,6 +192,7 @@ SIGNATURES = {
     "pti_rank_moments": (_I, [_P, _I, _I, _P, _P, _P]),
     "pti_joint_histogram_ws_bytes": (_I64, [_I, _I, _I, _I]),
     "pti_joint_histogram": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pti_ksg_counts": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pti_mask_compare_ws_bytes": (_I64, [_I, _I, _I]),
     "pti_mask_compare": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _I64, _P]),
 }

@@ -12,14 +12,22 @@ always comes from the config.  On the device: ONE call each of ``ops.tied_ranks`
 its minimum and maximum, numpy's ``histogram`` edges), all integer-exact; the tables come to the host in one packed copy and
 ``utils/disentanglement.py`` does the arithmetic.
 
+``--mi-estimator ksg`` puts the Kraskov-Stoegbauer-Grassberger k-nearest-neighbour estimate (estimator 1, the one under
+scikit-learn's ``mutual_info_regression``; ``--ksg-neighbors`` K, default 3) in the place of the histogram MI: MIG, modularity
+and interpretability are then formed from it, with the histogram entropies as MIG's denominators.  One more device call,
+``ops.ksg_counts``, on the columns scaled to unit deviation on the host (``utils.disentanglement.ksg_scale``); its integer
+counts come back whole and ``ksg_mutual_information`` applies the digammas.  Unlike ``mutual_info_regression`` no noise is
+added to break ties -- the result is deterministic -- and the scaling is done in fp64 and rounded to fp32 before upload.
+
 Outputs in ``--output-dir`` (default ``<run_dir>/ar_eval``):
 
 * ``disentanglement.json``: ``scores`` (``mig, modularity, sap, interpretability``), ``attributes`` (by name:
   ``latent_channel, spearman_rho, best_channel_spearman`` = argmax |rho| over the channels, ``mapped_channel_is_best, mig,
   sap``), the ``[na][L]`` matrices ``spearman_rho``, ``mutual_information`` (nats) and ``pearson_r``, ``entropy`` [na], ``bins``,
   ``n_images``, ``excluded`` (per score, the entries left out of its mean because they are undefined), ``args``, ``files``.  An
-  undefined value is ``null``.
-* ``disentanglement.png``: the |rho| and MI heat maps with the mapped cells outlined.
+  undefined value is ``null``.  With ``--mi-estimator ksg`` also ``mi_estimator``, ``ksg_neighbors`` and
+  ``mutual_information_binned`` (the histogram MI that ``mutual_information`` then no longer holds).
+* ``disentanglement.png``: the |rho| and MI heat maps with the mapped cells outlined; the MI panel names its estimator.
 """
 from __future__ import annotations
 
@@ -59,7 +67,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--bins", type=int, default=20, help="Equal-width bins per column of the MI histograms (default: 20).")
     p.add_argument("--from-npz", default=None, metavar="PATH",
                    help="channel_means.npz of an evaluate_ar_vae run: use its z / attrs / names, load no model")
+    p.add_argument("--mi-estimator", choices=("binned", "ksg"), default="binned",
+                   help="MI under MIG / modularity / interpretability: the --bins histograms (default) or the KSG "
+                        "k-nearest-neighbour estimate")
+    p.add_argument("--ksg-neighbors", type=int, default=3, metavar="K",
+                   help=f"Neighbour count of --mi-estimator ksg (default: 3; 1 .. {ops.KSG_MAX_K}).")
     args = p.parse_args(argv)
+    if not 1 <= args.ksg_neighbors <= ops.KSG_MAX_K:
+        p.error(f"--ksg-neighbors must lie in 1 .. {ops.KSG_MAX_K}")
     if args.from_npz is None and (args.checkpoint is None or args.input_dir is None):
         p.error("--checkpoint and --input-dir are required without --from-npz")
     if not 2 <= args.bins <= ops.DISENT_MAX_BINS:
@@ -102,6 +117,15 @@ def device_tables(z: torch.Tensor, attrs: torch.Tensor, bins: int):
     return packed[:a].numpy(), packed[a:b].reshape(m, m).numpy(), packed[b:c].reshape(counts.shape).numpy(), z_h
 
 
+def device_ksg(cols: np.ndarray, l: int, k: int, device):
+    """The device work of ``--mi-estimator ksg``: host columns ``cols`` [L + na, N] fp32 (channels first, already scaled) ->
+    host ``(nx, ny)``: int32 [na, L, N] each, in one copy."""
+    t = torch.from_numpy(np.ascontiguousarray(cols, dtype=np.float32)).to(device)
+    _, nx, ny = ops.ksg_counts(t[:l].t(), t[l:], k)
+    both = torch.stack([nx, ny]).cpu().numpy()
+    return both[0], both[1]
+
+
 def main(argv=None) -> None:
     args = parse_args(argv)
     config = load_vae_config(args.config_file)
@@ -113,6 +137,9 @@ def main(argv=None) -> None:
                          f"{ops.RANK_AGREEMENT_MAX_NA} x {ops.RANK_AGREEMENT_MAX_L}")
     device = init_device_and_seed(args.seed)
     resolved = vars(args).copy()
+    ksg = args.mi_estimator == "ksg"
+    if not ksg:                                    # the default report is the one this command has always written
+        del resolved["mi_estimator"], resolved["ksg_neighbors"]
     if args.from_npz is not None:
         z_np, attrs_h, files = load_npz(args.from_npz, settings.names)
         if z_np.shape[1] != latent_channels:
@@ -138,16 +165,26 @@ def main(argv=None) -> None:
         z = channel_means(model, loader, table.shape[0], latent_channels, device)
         files = [Path(p).name for p in paths]
     n = attrs_h.shape[1]
+    if ksg and not args.ksg_neighbors + 1 <= n <= ops.KSG_MAX_N:
+        raise SystemExit(f"{WHO}: {n} images; --mi-estimator ksg with {args.ksg_neighbors} neighbours takes "
+                         f"{args.ksg_neighbors + 1} .. {ops.KSG_MAX_N}")
     sums, gram, counts, z_h = device_tables(z, attrs, args.bins)
+    mi = None
+    if ksg:
+        nx, ny = device_ksg(D.ksg_scale(np.concatenate([z_h.T, attrs_h])), latent_channels, args.ksg_neighbors, device)
+        mi = D.ksg_mutual_information(nx, ny, n, args.ksg_neighbors)
     report = D.disentanglement_report(settings.names, settings.channels, n, sums, gram, counts,
-                                      ar_metrics.pearson_matrix(z_h, attrs_h))
+                                      ar_metrics.pearson_matrix(z_h, attrs_h), mi=mi)
     report.update(bins=args.bins, n_images=n, args=resolved, files=files)
+    if ksg:
+        report.update(mi_estimator="ksg", ksg_neighbors=args.ksg_neighbors)
     out_dir = Path(args.output_dir) if args.output_dir is not None else resolve_run_dir(vars(config), args.config_file) / "ar_eval"
     out_dir.mkdir(parents=True, exist_ok=True)
     with (out_dir / "disentanglement.json").open("w", encoding="utf-8") as handle:
         json.dump(report, handle, indent=2, allow_nan=False)
+    title = {"mi_title": f"mutual information (nats), KSG k = {args.ksg_neighbors}"} if ksg else {}
     D.save_heatmaps(out_dir / "disentanglement.png", report["spearman_rho"], report["mutual_information"], settings.names,
-                    settings.channels)
+                    settings.channels, **title)
     for name, entry in report["attributes"].items():
         rho = entry["spearman_rho"]
         print(f"   {name}: channel {entry['latent_channel']} rho {'n/a' if rho is None else format(rho, '+.4f')} "

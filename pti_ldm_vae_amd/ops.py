@@ -1531,6 +1531,68 @@ def joint_histogram(z, attrs, edges_z, edges_a, *, out=None):
     return bins_z, bins_a, counts
 
 
+# ---- k-nearest-neighbour mutual information (csrc/ksg.hip; include/pti_vae.h "k-nearest-neighbour mutual information") ----
+KSG_MAX_K, KSG_MAX_N = 16, 32768   # the bounds of pti_ksg_counts (L and na: RANK_AGREEMENT_MAX_L / _NA)
+
+
+def ksg_counts(z, attrs, k, *, out=None):
+    """Neighbour radii and range counts of the KSG mutual-information estimator for every (attribute, latent channel)
+    (``pti_ksg_counts``) -> ``(eps, nx, ny)`` device tensors.
+
+    ``z``: floating-point device matrix ``[N, L]`` in any layout -- a transposed view of a channel-major ``[L, N]`` buffer,
+    row stride included, is used in place, anything else is copied once; ``attrs``: ``[na, N]`` with dense rows; ``k``: the
+    neighbour count.  With ``dx = |x_i - x_j|``, ``dy = |y_i - y_j|`` (one fp32 subtraction each) for the channel ``x`` and the
+    attribute ``y`` of a pair: ``eps`` fp32 ``[na, L, N]`` is the ``k``-th smallest ``max(dx, dy)`` over the OTHER rows, ``nx`` /
+    ``ny`` int32 ``[na, L, N]`` count the other rows with ``dx`` / ``dy`` at most the largest fp32 below ``eps`` (at most 0 when
+    ``eps == 0``: exact duplicates) -- scikit-learn's ``_compute_mi_cc`` before its digammas; ``utils.disentanglement.
+    ksg_mutual_information`` turns the counts into MI.  ``out=(eps, nx, ny)`` are written in place.  1 <= k <= 16,
+    k + 1 <= N <= 32768, L <= 16, na <= 16.  A non-finite value is refused with a ValueError that names its column -- the
+    one check that reads a device result back (one host synchronisation per call).  Runs on the current stream; exact,
+    bitwise reproducible, no scratch buffer."""
+    who = "ksg_counts"
+    for name, t in (("z", z), ("attrs", attrs)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
+        if not t.is_floating_point():
+            raise TypeError(f"{who}: {name}: expected a floating-point matrix, got {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"{who}: {name}: expected a matrix, got {tuple(t.shape)}")
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"{who}: k: expected an int, got {type(k).__name__}")
+    n, l = z.shape
+    na = attrs.shape[0]
+    if attrs.shape[1] != n or attrs.device != z.device:
+        raise ValueError(f"{who}: z {tuple(z.shape)} needs attrs [na, {n}] on {z.device}, got {tuple(attrs.shape)} on {attrs.device}")
+    if not 1 <= k <= KSG_MAX_K:
+        raise ValueError(f"{who}: k = {k} out of range (1 <= k <= {KSG_MAX_K})")
+    if not (k + 1 <= n <= KSG_MAX_N and 1 <= l <= RANK_AGREEMENT_MAX_L and 1 <= na <= RANK_AGREEMENT_MAX_NA):
+        raise ValueError(f"{who}: unsupported shape z {tuple(z.shape)} attrs {tuple(attrs.shape)} k {k} (k + 1 <= N <= {KSG_MAX_N}, "
+                         f"1 <= L <= {RANK_AGREEMENT_MAX_L}, 1 <= na <= {RANK_AGREEMENT_MAX_NA})")
+    zt = z.t()                                               # [L, N]: the kernel reads channel-major rows
+    if zt.dtype != F32:
+        zt = zt.to(F32)
+    if zt.stride(1) != 1 or zt.stride(0) < n:
+        zt = zt.contiguous()
+    attrs = _rows(attrs, f"{who}: attrs")
+    bad = torch.cat([~torch.isfinite(zt).all(1), ~torch.isfinite(attrs).all(1)])
+    if bool(bad.any()):                                      # the host synchronisation of this wrapper
+        col = int(bad.nonzero()[0])
+        raise ValueError(f"{who}: {'channel ' + str(col) if col < l else 'attribute ' + str(col - l)} holds a non-finite value")
+    if out is None:
+        out = (None, None, None)
+    eps = _out(out[0], (na, l, n), F32, z.device, f"{who}: out[0] (eps)")
+    nx = _out(out[1], (na, l, n), torch.int32, z.device, f"{who}: out[1] (nx)")
+    ny = _out(out[2], (na, l, n), torch.int32, z.device, f"{who}: out[2] (ny)")
+    ldz, lda = (zt.stride(0) if l > 1 else n), (attrs.stride(0) if na > 1 else n)   # a single row's stride means nothing
+    prof = KERNEL_PROFILE
+    rec = None if prof is None else _prof_begin(prof)
+    L.check(L.lib().pti_ksg_counts(_ptr(zt), ldz, _ptr(attrs), lda, n, l, na, k, _ptr(eps), _ptr(nx), _ptr(ny), _stream()),
+            "pti_ksg_counts")
+    if rec is not None:   # both columns of a pair are read twice per row tile; three outputs
+        _prof_end(rec, 0.0, 4.0 * l * na * n * (4 * ((n + 255) // 256) + 3), ("ksg_counts", l, na, n, k))
+    return eps, nx, ny
+
+
 # ---- PatchDiscriminator passes (csrc/discriminator.hip; include/pti_vae.h "PatchDiscriminator") -----------------------
 def pd_out_hw(h, w, stride):
     return (h + 2 - 4) // stride + 1, (w + 2 - 4) // stride + 1

@@ -68,6 +68,53 @@ def mutual_information(counts):
     return mi, h
 
 
+EULER_GAMMA = 0.5772156649015328606
+
+
+def ksg_scale(cols) -> np.ndarray:
+    """What the k-nearest-neighbour estimator sees: every column (a ROW of ``cols`` [M, N]) divided by its population
+    standard deviation -- fp64 arithmetic on the fp32 data, rounded back to fp32, ``sklearn.preprocessing.scale(x,
+    with_mean=False)``.  A column whose deviation is below ``10 eps`` (fp64) -- a constant column -- is left unscaled, as
+    sklearn leaves it."""
+    x = np.asarray(cols, dtype=np.float32).astype(np.float64)
+    if x.ndim != 2:
+        raise ValueError(f"ksg_scale: expected columns [M, N], got {x.shape}")
+    std = x.std(axis=1)
+    std[~(std >= 10.0 * np.finfo(np.float64).eps)] = 1.0
+    return (x / std[:, None]).astype(np.float32)
+
+
+def digamma_table(n) -> np.ndarray:
+    """``psi(m) = -gamma + H_(m - 1)`` at the integers ``m = 1 .. n`` as fp64 ``[n + 1]``, indexed by ``m`` (entry 0, the pole,
+    is ``-inf``); the harmonic numbers are one running fp64 sum.  No scipy needed."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"digamma_table: n = {n} (n >= 1)")
+    table = np.full(n + 1, -np.inf)
+    table[1] = -EULER_GAMMA
+    table[2:] = np.cumsum(1.0 / np.arange(1, n, dtype=np.float64)) - EULER_GAMMA
+    return table
+
+
+def ksg_mutual_information(nx, ny, n, k) -> np.ndarray:
+    """The Kraskov-Stoegbauer-Grassberger estimate (estimator 1, scikit-learn's ``_compute_mi_cc``) from the integer range
+    counts of ``ops.ksg_counts``: ``nx``, ``ny`` int [na, L, n] -> fp64 MI [na, L] in nats,
+    ``max(0, psi(n) + psi(k) - mean_i psi(nx_i + 1) - mean_i psi(ny_i + 1))``.  The mean is taken over the per-row terms
+    ``(psi(n) - psi(nx_i + 1)) + (psi(k) - psi(ny_i + 1))``: where every ``nx_i = n - 1`` and ``ny_i = k - 1`` -- a constant
+    column against one without ties -- each term, and with it the estimate, is 0.0 exactly."""
+    nx, ny = np.asarray(nx), np.asarray(ny)
+    n, k = int(n), int(k)
+    if nx.shape != ny.shape or nx.ndim != 3 or nx.shape[2] != n:
+        raise ValueError(f"ksg_mutual_information: expected nx, ny [na, L, {n}], got {nx.shape} and {ny.shape}")
+    if not 1 <= k <= n - 1:
+        raise ValueError(f"ksg_mutual_information: k = {k} with n = {n} (1 <= k <= n - 1)")
+    if nx.min() < 0 or ny.min() < 0 or nx.max() > n - 1 or ny.max() > n - 1:
+        raise ValueError(f"ksg_mutual_information: a count outside 0 .. {n - 1}")
+    psi = digamma_table(n)
+    terms = (psi[n] - psi[nx.astype(np.int64) + 1]) + (psi[k] - psi[ny.astype(np.int64) + 1])
+    return np.maximum(terms.mean(axis=2), 0.0)
+
+
 def _top_two_gap(values):
     """Largest minus second largest of the defined values; ``None`` with fewer than two."""
     top = sorted((v for v in values if v is not None), reverse=True)
@@ -125,12 +172,21 @@ def best_channel(rho_row):
     return best
 
 
-def disentanglement_report(names, channels, n, sums, gram, counts, pearson) -> dict:
-    """The ``scores``, ``attributes``, matrices, ``entropy`` and ``excluded`` blocks of ``disentanglement.json``."""
+def disentanglement_report(names, channels, n, sums, gram, counts, pearson, *, mi=None) -> dict:
+    """The ``scores``, ``attributes``, matrices, ``entropy`` and ``excluded`` blocks of ``disentanglement.json``.  ``mi``
+    [na, L] (``ksg_mutual_information``) takes the place of the histogram MI in ``mutual_information`` and under the scores;
+    the histogram MI is then kept as ``mutual_information_binned``.  The entropies stay the histogram ones: a differential
+    entropy cannot normalise MIG."""
     counts = np.asarray(counts)
     na, l = counts.shape[:2]
     rho = spearman_matrix(sums, gram, n, na, l)
-    mi, h = mutual_information(counts)
+    binned, h = mutual_information(counts)
+    if mi is None:
+        mi = binned
+    else:
+        mi = np.asarray(mi, dtype=np.float64)
+        if mi.shape != (na, l):
+            raise ValueError(f"disentanglement_report: expected mi [{na}, {l}], got {mi.shape}")
     s = scores(mi, h, pearson, list(names))
     per_attr = {}
     for q, name in enumerate(names):
@@ -140,13 +196,16 @@ def disentanglement_report(names, channels, n, sums, gram, counts, pearson) -> d
         per_attr[name] = {"latent_channel": ch, "spearman_rho": rho[q][ch] if mapped else None,
                           "best_channel_spearman": best, "mapped_channel_is_best": bool(mapped and best == ch),
                           "mig": s["per_attribute"]["mig"][q], "sap": s["per_attribute"]["sap"][q]}
-    return {"scores": s["scores"], "attributes": per_attr, "spearman_rho": rho, "mutual_information": mi.tolist(),
-            "pearson_r": pearson, "entropy": h.tolist(), "excluded": s["excluded"]}
+    report = {"scores": s["scores"], "attributes": per_attr, "spearman_rho": rho, "mutual_information": mi.tolist(),
+              "pearson_r": pearson, "entropy": h.tolist(), "excluded": s["excluded"]}
+    if mi is not binned:
+        report["mutual_information_binned"] = binned.tolist()
+    return report
 
 
-def save_heatmaps(path, rho, mi, names, channels) -> Path:
+def save_heatmaps(path, rho, mi, names, channels, mi_title="mutual information (nats)") -> Path:
     """|rho| and MI heat maps side by side: attributes down, channels across, the mapped cell of every attribute outlined
-    (matplotlib, Agg; the drawing style of ``ar_metrics.save_tau_heatmap``)."""
+    (matplotlib, Agg; the drawing style of ``ar_metrics.save_tau_heatmap``).  ``mi_title``: the MI panel's title."""
     import matplotlib
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt
@@ -155,7 +214,7 @@ def save_heatmaps(path, rho, mi, names, channels) -> Path:
              np.array(mi, dtype=np.float64)]
     na, l = grids[0].shape
     fig, axes = plt.subplots(1, 2, figsize=(2 * (1.5 + 0.6 * l), 1.2 + 0.5 * na))
-    for ax, grid, title, cmap, vmax in zip(axes, grids, ("|Spearman rho|: attribute vs channel mean", "mutual information (nats)"),
+    for ax, grid, title, cmap, vmax in zip(axes, grids, ("|Spearman rho|: attribute vs channel mean", mi_title),
                                            ("viridis", "magma"), (1.0, None)):
         im = ax.imshow(np.ma.masked_invalid(grid), cmap=cmap, vmin=0.0, vmax=vmax, aspect="auto")
         ax.set_xticks(range(l), [str(c) for c in range(l)])

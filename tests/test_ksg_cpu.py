@@ -1,0 +1,312 @@
+"""CPU tests of the k-nearest-neighbour (KSG) mutual information: the numpy oracle against scikit-learn's ``_compute_mi_cc``
+and against its committed golden file, the mutations of the oracle that the checks must catch, the host arithmetic of
+``utils.disentanglement`` (``ksg_scale``, ``digamma_table``, ``ksg_mutual_information``), the pieces of the command that need
+no GPU, and the refusals of ``pti_ksg_counts`` (it returns before any launch).
+
+Measured here: the oracle's MI differs from ``_compute_mi_cc`` by at most 1.3e-15 on the cases below (bound 1e-12: another
+order of summation); ``digamma_table`` deviates from ``scipy.special.digamma`` by at most 7.5e-14 over 1 .. 32768 (at 27110:
+the rounding of one running fp64 sum), and the gate is ten times that."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+import ksg_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DIGAMMA_MEASURED = 7.5e-14          # max |digamma_table - scipy.special.digamma| over 1 .. 32768, measured on the CPU
+SMALL = ("n2", "n4", "n17", "n65", "n257", "ties", "kth_tie", "const", "tiny")   # recomputed in full by the CPU tests
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return {case.name: case for case in O.all_cases()}
+
+
+@pytest.fixture(scope="module")
+def tables(cases):
+    """{(case name, k): oracle tables} of the small cases: computed once and shared, never modified."""
+    return {(name, k): O.case_tables(cases[name].z, cases[name].attrs, k) for name in SMALL for k in cases[name].ks}
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return O.load_golden()
+
+
+def test_case_list_is_the_specified_one(cases):
+    assert [(name, n, l, na, ks) for name, n, l, na, ks, *_ in O.CASES] == [
+        ("n2", 2, 1, 1, (1,)), ("n4", 4, 1, 1, (3,)), ("n17", 17, 2, 1, (16,)), ("n65", 65, 2, 2, (3,)), ("n257", 257, 10, 6, (3,)),
+        ("n1030", 1030, 16, 16, (5,)), ("n2500", 2500, 2, 2, (1, 16)), ("ties", 300, 3, 3, (3,)), ("kth_tie", 64, 1, 1, (3,)),
+        ("const", 97, 2, 2, (3,)), ("tiny", 33, 1, 1, (3,))]
+    assert O.CASES[6][7][0] > 0 and O.CASES[6][7][1] > 0                                  # padded strides on the GPU
+    ties = cases["ties"]
+    assert len(set(ties.attrs[0].tolist())) == 5 and len(set(ties.attrs[1].tolist())) == 21
+    values, counts = np.unique(ties.z[:, 1], return_counts=True)
+    assert counts.max() == 40
+    const = cases["const"]
+    assert np.all(const.z[:, 1] == const.z[0, 1]) and np.all(const.attrs[1] == const.attrs[1, 0])
+    tiny = cases["tiny"]
+    both = np.concatenate([tiny.z.ravel(), tiny.attrs.ravel()])
+    assert np.all(np.abs(both) < np.finfo(np.float32).tiny) and 5e-41 < np.abs(both).max() < 2e-40    # all subnormal
+    assert np.any(np.signbit(tiny.z[:, 0]) & (tiny.z[:, 0] == 0)) and np.any(~np.signbit(tiny.z[:, 0]) & (tiny.z[:, 0] == 0))
+    for name in ("n65", "n257", "n2500"):                      # the dyadic grid: fp32 and fp64 differences coincide
+        z = cases[name].z.astype(np.float64)
+        assert np.array_equal(np.round(z / O.GRID) * O.GRID, z)
+
+
+def test_oracle_reproduces_the_golden_file(cases, tables, gold):
+    want = sorted([f"{name}/spec" for name in cases]
+                  + [f"{name}/k{k}/{t}" for name, case in cases.items() for k in case.ks for t in O.TABLES + ("mi",)])
+    assert sorted(gold) == want and os.path.getsize(O.GOLDEN) < 1 << 20
+    for spec in O.CASES:
+        assert gold[f"{spec[0]}/spec"].tolist() == [spec[1], spec[2], spec[3], spec[5]]
+    for (name, k), t in tables.items():
+        for key in O.TABLES:
+            assert np.array_equal(gold[f"{name}/k{k}/{key}"], t[key]), (name, k, key)
+        assert gold[f"{name}/k{k}/eps"].dtype == np.float32 and gold[f"{name}/k{k}/nx"].dtype == np.int16
+        assert np.max(np.abs(gold[f"{name}/k{k}/mi"] - t["mi"])) <= 1e-12, (name, k)
+    for name, k, pairs in (("n1030", 5, ((0, 0), (7, 11), (15, 15))), ("n2500", 1, ((1, 0),)), ("n2500", 16, ((0, 1),))):
+        case = cases[name]                                     # the large cases: a few pairs each
+        for q, c in pairs:
+            eps, nx, ny = O.pair_tables(case.z[:, c], case.attrs[q], k)
+            assert np.array_equal(gold[f"{name}/k{k}/eps"][q, c], eps) and np.array_equal(gold[f"{name}/k{k}/nx"][q, c], nx)
+            assert np.array_equal(gold[f"{name}/k{k}/ny"][q, c], ny), (name, k, q, c)
+            assert abs(gold[f"{name}/k{k}/mi"][q, c] - O.mutual_information(nx, ny, case.n, k)) <= 1e-12
+
+
+def test_tables_are_consistent(cases, tables):
+    for (name, k), t in tables.items():
+        n = cases[name].n
+        assert t["eps"].min() >= 0 and np.all(np.isfinite(t["eps"])), name
+        assert t["nx"].min() >= 0 and t["ny"].min() >= 0 and t["nx"].max() <= n - 1 and t["ny"].max() <= n - 1, name
+    pair = tables[("n2", 1)]                                   # two rows: the smaller of dx, dy lies inside the other one
+    assert np.all(pair["nx"] + pair["ny"] == 1) and np.all(tables[("n4", 3)]["eps"] > 0)
+    lattice = tables[("kth_tie", 3)]                           # every lattice point has 3 .. 8 neighbours at distance 1
+    assert np.all(lattice["eps"] == 1.0) and np.all(lattice["nx"] == 7) and np.all(lattice["ny"] == 7)
+    ties = tables[("ties", 3)]
+    assert int((ties["eps"] == 0).sum()) >= 20 and ties["nx"][ties["eps"] == 0].min() >= 3      # the duplicates are counted
+    tiny = tables[("tiny", 3)]
+    assert np.all(tiny["eps"][0, 0, :4] == 0) and np.all(tiny["nx"][0, 0, :4] == 3) and np.all(tiny["ny"][0, 0, :4] == 3)
+    assert 0 < tiny["eps"][0, 0, 4:].min() and tiny["eps"].max() < np.finfo(np.float32).tiny         # subnormal radii
+
+
+def test_oracle_equals_sklearn(cases, tables, gold):
+    mi_cc = pytest.importorskip("sklearn.feature_selection._mutual_info")._compute_mi_cc
+    worst = 0.0
+    for (name, k), t in tables.items():
+        if name == "tiny":                                     # fp64 would tell 1e-40 apart just as well; left to the fp32 rule
+            continue
+        case = cases[name]
+        for q in range(case.na):
+            for c in range(min(case.l, 3)):
+                want = mi_cc(case.z[:, c].astype(np.float64), case.attrs[q].astype(np.float64), k)
+                worst = max(worst, abs(t["mi"][q, c] - want))
+                assert abs(t["mi"][q, c] - want) <= 1e-12, (name, k, q, c, t["mi"][q, c], want)
+    for name, k, q, c in (("n1030", 5, 3, 10), ("n2500", 1, 0, 1), ("n2500", 16, 1, 1)):
+        case = cases[name]
+        want = mi_cc(case.z[:, c].astype(np.float64), case.attrs[q].astype(np.float64), k)
+        worst = max(worst, abs(gold[f"{name}/k{k}/mi"][q, c] - want))
+        assert abs(gold[f"{name}/k{k}/mi"][q, c] - want) <= 1e-12, (name, k)
+    print(f"oracle vs _compute_mi_cc: MI differs by at most {worst:.3e}")
+
+
+def test_digamma_table_against_scipy():
+    digamma = pytest.importorskip("scipy.special").digamma
+    from pti_ldm_vae_amd.utils.disentanglement import digamma_table
+    table = digamma_table(32768)
+    assert table.dtype == np.float64 and table.shape == (32769,) and table[0] == -np.inf and table[1] == -O.EULER_GAMMA
+    dev = np.abs(table[1:] - digamma(np.arange(1, 32769, dtype=np.float64)))
+    print(f"digamma_table vs scipy: max deviation {dev.max():.3e} at m = {1 + int(dev.argmax())}")
+    assert dev.max() <= 10 * DIGAMMA_MEASURED
+    assert np.array_equal(digamma_table(5), table[:6]) and np.array_equal(digamma_table(1), table[:2])
+    assert np.max(np.abs(table[1:] - O.digamma_int(32768)[1:])) <= 10 * DIGAMMA_MEASURED         # the oracle's own table
+    with pytest.raises(ValueError):
+        digamma_table(0)
+
+
+def test_host_arithmetic_reproduces_the_oracle(cases, gold):
+    from pti_ldm_vae_amd.utils.disentanglement import ksg_mutual_information
+    for name, case in cases.items():
+        for k in case.ks:
+            nx, ny = gold[f"{name}/k{k}/nx"], gold[f"{name}/k{k}/ny"]
+            mi = ksg_mutual_information(nx, ny, case.n, k)
+            assert mi.dtype == np.float64 and mi.shape == (case.na, case.l) and mi.min() >= 0.0
+            assert np.max(np.abs(mi - gold[f"{name}/k{k}/mi"])) <= 1e-12, (name, k)
+            assert np.array_equal(mi, ksg_mutual_information(nx.astype(np.int32), ny.astype(np.int64), case.n, k))
+    mi = ksg_mutual_information(gold["const/k3/nx"], gold["const/k3/ny"], 97, 3)
+    assert mi[1].tolist() == [0.0, 0.0] and mi[0, 1] == 0.0                       # a constant side: exactly 0.0, not 1e-17
+    assert np.all(gold["const/k3/nx"][:, 1] == 96) and np.all(gold["const/k3/ny"][0, 1] == 2)     # ... from n - 1 and k - 1
+    with pytest.raises(ValueError):
+        ksg_mutual_information(np.zeros((1, 1, 5), int), np.zeros((1, 1, 4), int), 5, 3)
+    with pytest.raises(ValueError):
+        ksg_mutual_information(np.zeros((1, 1, 5), int), np.zeros((1, 1, 5), int), 5, 5)          # k = n
+    with pytest.raises(ValueError):
+        ksg_mutual_information(np.full((1, 1, 5), 5), np.zeros((1, 1, 5), int), 5, 3)             # a count of n
+
+
+def test_ksg_scale_equals_sklearn():
+    scale = pytest.importorskip("sklearn.preprocessing").scale
+    from pti_ldm_vae_amd.utils.disentanglement import ksg_scale
+    rng = np.random.default_rng(3)
+    cols = rng.normal(2.0, 3.0, (7, 500)).astype(np.float32)
+    cols[3] = 0.3                                              # a constant column
+    cols[5] *= np.float32(1e-3)
+    got = ksg_scale(cols)
+    want = scale(cols.T.astype(np.float64), with_mean=False).astype(np.float32).T
+    assert got.dtype == np.float32 and got.shape == cols.shape and np.array_equal(got, want)
+    assert np.array_equal(got[3], cols[3])                     # left unscaled
+    assert np.allclose(got[[0, 1, 2, 4, 5, 6]].astype(np.float64).std(axis=1), 1.0, atol=1e-6)
+    assert np.array_equal(ksg_scale(cols.astype(np.float64)), got)
+    with pytest.raises(ValueError):
+        ksg_scale(cols[0])
+
+
+MUTATIONS = {"include_self": ("n65", "kth_tie"), "le_eps": ("kth_tie", "n65"), "no_zero_rule": ("ties", "tiny"),
+             "euclidean": ("n65", "kth_tie")}
+
+
+@pytest.mark.parametrize("mutation", sorted(MUTATIONS))
+def test_a_mutated_oracle_is_caught(cases, tables, mutation):
+    """Each wrong definition changes an exact table -- a radius or a count -- on the cases that are there for it."""
+    anywhere = set()
+    for name in MUTATIONS[mutation]:
+        case, k = cases[name], cases[name].ks[0]
+        m = O.case_tables(case.z, case.attrs, k, **{mutation: True})
+        t = tables[(name, k)]
+        changed = {key for key in O.TABLES if not np.array_equal(m[key], t[key])}
+        assert changed, (mutation, name)
+        anywhere |= changed
+    if mutation in ("le_eps", "no_zero_rule"):                 # the radius is the same one: only the counting differs
+        assert anywhere <= {"nx", "ny"}, (mutation, anywhere)
+    else:
+        assert "eps" in anywhere, (mutation, anywhere)
+    if mutation == "no_zero_rule":                             # without duplicates the strict rule is the same rule
+        case = cases["n65"]
+        m = O.case_tables(case.z, case.attrs, 3, no_zero_rule=True)
+        assert all(np.array_equal(m[key], tables[("n65", 3)][key]) for key in O.TABLES)
+
+
+def test_argument_parsing():
+    from pti_ldm_vae_amd import evaluate_disentanglement as E
+    from pti_ldm_vae_amd import ops
+    assert (ops.KSG_MAX_K, ops.KSG_MAX_N) == (16, 32768)
+    a = E.parse_args(["-c", "cfg.json", "--checkpoint", "w.pth", "--input-dir", "imgs"])
+    assert (a.mi_estimator, a.ksg_neighbors, a.bins) == ("binned", 3, 20)
+    a = E.parse_args(["-c", "c", "--from-npz", "m.npz", "--mi-estimator", "ksg", "--ksg-neighbors", "16", "--bins", "8"])
+    assert (a.mi_estimator, a.ksg_neighbors, a.bins, a.from_npz) == ("ksg", 16, 8, "m.npz")
+    assert E.parse_args(["-c", "c", "--from-npz", "m.npz", "--ksg-neighbors", "1"]).ksg_neighbors == 1
+    for bad in (["--mi-estimator", "kernel"], ["--ksg-neighbors", "0"], ["--ksg-neighbors", "17"], ["--ksg-neighbors", "2.5"],
+                ["--mi-estimator"]):
+        with pytest.raises(SystemExit):
+            E.parse_args(["-c", "c", "--from-npz", "m.npz"] + bad)
+
+
+TODAYS_KEYS = {"scores", "attributes", "spearman_rho", "mutual_information", "pearson_r", "entropy", "bins", "n_images",
+               "excluded", "args", "files"}
+TODAYS_ARGS = {"config_file", "checkpoint", "input_dir", "attributes_path", "output_dir", "batch_size", "num_samples",
+               "num_workers", "seed", "random_init_vae", "bins", "from_npz"}
+
+
+def test_report_keys_with_a_stubbed_device_layer(tmp_path, monkeypatch):
+    """With the device layer replaced by the oracles the command runs on the CPU: the default report has exactly today's
+    keys (``args`` included), the ksg report exactly three more, and its scores come from the KSG matrix and the histogram
+    entropies."""
+    import disentanglement_oracle as DO
+    import torch
+    from pti_ldm_vae_amd import evaluate_disentanglement as E
+    from pti_ldm_vae_amd.utils import disentanglement as D
+    cfg = json.load(open(os.path.join(ROOT, "config", "ar_vae_dente_kl1e3.json")))
+    names = [k for k in cfg["regularized_attributes"]["attribute_latent_mapping"] if not k.startswith("_")]
+    cfg["run_dir"] = str(tmp_path / "run")
+    cf = tmp_path / "ar.json"
+    cf.write_text(json.dumps(cfg))
+    case = DO.make_case("cli", 40, 10, len(names), 5, "plain", 20)
+    npz = tmp_path / "channel_means.npz"
+    np.savez(npz, z=case.z, attrs=case.attrs, names=np.array(names), files=np.array([f"img_{i:03d}.tif" for i in range(case.n)]))
+    calls = []
+
+    def tables(z, attrs, bins):
+        r = DO.report(z.numpy(), attrs.numpy(), bins)
+        return r["sums"], r["gram"], r["counts"].astype(np.int64), z.numpy()
+
+    def ksg(cols, l, k, device):
+        calls.append((cols.copy(), l, k))
+        t = O.case_tables(cols[:l].T, cols[l:], k)
+        return t["nx"], t["ny"]
+
+    monkeypatch.setattr(E, "init_device_and_seed", lambda seed: torch.device("cpu"))
+    monkeypatch.setattr(E, "device_tables", tables)
+    monkeypatch.setattr(E, "device_ksg", ksg)
+    monkeypatch.setattr(E, "load_model", lambda *a, **k: pytest.fail("--from-npz must not load a model"))
+    E.main(["-c", str(cf), "--from-npz", str(npz), "--output-dir", str(tmp_path / "binned")])
+    binned = json.loads((tmp_path / "binned" / "disentanglement.json").read_text())
+    assert set(binned) == TODAYS_KEYS and set(binned["args"]) == TODAYS_ARGS and calls == []
+    E.main(["-c", str(cf), "--from-npz", str(npz), "--output-dir", str(tmp_path / "ksg"), "--mi-estimator", "ksg",
+            "--ksg-neighbors", "4"])
+    doc = json.loads((tmp_path / "ksg" / "disentanglement.json").read_text())
+    assert set(doc) == TODAYS_KEYS | {"mutual_information_binned", "mi_estimator", "ksg_neighbors"}
+    assert doc["mi_estimator"] == "ksg" and doc["ksg_neighbors"] == 4
+    assert set(doc["args"]) == TODAYS_ARGS | {"mi_estimator", "ksg_neighbors"}
+    assert doc["mutual_information_binned"] == binned["mutual_information"] and doc["entropy"] == binned["entropy"]
+    for key in ("spearman_rho", "pearson_r", "bins", "n_images", "files"):
+        assert doc[key] == binned[key], key
+    assert len(calls) == 1 and calls[0][1:] == (10, 4)
+    cols = np.concatenate([case.z.T, case.attrs])
+    assert calls[0][0].dtype == np.float32 and np.array_equal(calls[0][0], D.ksg_scale(cols))   # the kernel is fed scaled columns
+    want = O.case_tables(D.ksg_scale(cols)[:10].T, D.ksg_scale(cols)[10:], 4)["mi"]
+    assert np.max(np.abs(np.array(doc["mutual_information"]) - want)) <= 1e-12
+    assert doc["mutual_information"] != doc["mutual_information_binned"]
+    s = D.scores(np.array(doc["mutual_information"]), np.array(doc["entropy"]), doc["pearson_r"], names)
+    assert doc["scores"] == s["scores"] and doc["excluded"] == s["excluded"]
+    assert [doc["attributes"][k]["mig"] for k in names] == s["per_attribute"]["mig"]
+    from PIL import Image
+    with Image.open(tmp_path / "ksg" / "disentanglement.png") as im:
+        assert im.format == "PNG"
+    np.savez(npz, z=case.z[:4], attrs=case.attrs[:, :4], names=np.array(names))
+    with pytest.raises(SystemExit, match="4 images"):
+        E.main(["-c", str(cf), "--from-npz", str(npz), "--mi-estimator", "ksg", "--ksg-neighbors", "4"])
+
+
+def test_report_takes_a_replacement_mi_matrix():
+    import disentanglement_oracle as DO
+    from pti_ldm_vae_amd.utils import disentanglement as D
+    from pti_ldm_vae_amd.utils.ar_metrics import pearson_matrix
+    case = DO.make_case("r", 50, 4, 3, 9, "plain", 8)
+    r = DO.report(case.z, case.attrs, 8)
+    pearson = pearson_matrix(case.z, case.attrs)
+    names = ["a", "b", "c"]
+    base = D.disentanglement_report(names, case.channels, case.n, r["sums"], r["gram"], r["counts"], pearson)
+    assert "mutual_information_binned" not in base
+    mi = np.arange(12, dtype=np.float64).reshape(3, 4) / 10
+    doc = D.disentanglement_report(names, case.channels, case.n, r["sums"], r["gram"], r["counts"], pearson, mi=mi)
+    assert doc["mutual_information"] == mi.tolist() and doc["mutual_information_binned"] == base["mutual_information"]
+    assert doc["entropy"] == base["entropy"] and doc["spearman_rho"] == base["spearman_rho"]
+    assert doc["scores"] == D.scores(mi, np.array(base["entropy"]), pearson, names)["scores"]
+    with pytest.raises(ValueError):
+        D.disentanglement_report(names, case.channels, case.n, r["sums"], r["gram"], r["counts"], pearson, mi=mi[:2])
+
+
+def test_entry_point_refusals():
+    """PTI_EINVAL (-1) / PTI_EUNSUPPORTED (-2) before any launch; pointers are never dereferenced on these paths."""
+    from pti_ldm_vae_amd import _lib as L
+    h = L.lib()
+    assert h.pti_abi_version() == 5
+    p = C.c_void_p(4096)
+
+    def ksg(zt=p, ldz=100, attrs=p, lda=100, n=100, l=4, na=2, k=3, eps=p, nx=p, ny=p):
+        return h.pti_ksg_counts(zt, ldz, attrs, lda, n, l, na, k, eps, nx, ny, None)
+
+    for kw in (dict(zt=None), dict(attrs=None), dict(eps=None), dict(nx=None), dict(ny=None)):
+        assert ksg(**kw) == -1 and b"null" in h.pti_last_error_string(), kw
+    assert ksg(k=0) == -1 and b"ksg_counts" in h.pti_last_error_string()
+    assert ksg(l=0) == -1 and ksg(na=0) == -1 and ksg(n=3) == -1 and ksg(n=1, k=1) == -1 and ksg(n=16, k=16) == -1
+    assert ksg(k=17) == -2 and b"unsupported" in h.pti_last_error_string()
+    assert ksg(n=32769, ldz=40000, lda=40000) == -2 and ksg(l=17) == -2 and ksg(na=17) == -2
+    assert ksg(ldz=99) == -1 and b"stride" in h.pti_last_error_string()
+    assert ksg(lda=99) == -1
+    for kw in (dict(zt=C.c_void_p(4098)), dict(attrs=C.c_void_p(4098)), dict(eps=C.c_void_p(4098)), dict(nx=C.c_void_p(4097)),
+               dict(ny=C.c_void_p(4099))):
+        assert ksg(**kw) == -1 and b"misaligned" in h.pti_last_error_string(), kw
