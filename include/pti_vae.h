@@ -43,7 +43,9 @@ typedef void* pti_stream_t; /* hipStream_t */
                                Still 5: pti_umap_knn_cross / pti_umap_transform_graph (+ its _ws_floats) /
                                pti_umap_transform_layout appended in the same way.
                                Still 5: pti_display_planes appended in the same way.
-                               Still 5: pti_mask_compare / pti_mask_compare_ws_bytes appended in the same way. */
+                               Still 5: pti_mask_compare / pti_mask_compare_ws_bytes appended in the same way.
+                               Still 5: pti_neighbor_ranks / pti_segment_row_sums / pti_projection_distances appended in the
+                               same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -811,6 +813,32 @@ int pti_ksg_counts(const float* zt, int64_t ldz, const float* attrs, int64_t lda
 int64_t pti_mask_compare_ws_bytes(int n, int h, int w);
 int pti_mask_compare(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts, double* sums,
                      void* workspace, int64_t ws_bytes, pti_stream_t s);
+
+/* ---- projection quality of the latent-space analysis (scikit-learn: manifold.trustworthiness, metrics.silhouette_samples;
+ *      csrc/projection_quality.hip) ----
+ * dist: fp32 [n][n], row stride ldd in ELEMENTS (ldd >= n), used in place; 3 <= n <= 8192.
+ * pti_neighbor_ranks: nbr_idx int32 [n][m] dense, 1 <= m <= 256.  With j = nbr_idx[i][c],
+ *     out[i][c] = 1 + #{ l != i : key(i, l) < key(i, j) },   key(i, l) = (bits of dist[i][l], -0 taken as 0) << 32 | l,
+ *   pti_umap_knn's key: equal distances go to the lower column, and { j : rank <= k } is what pti_umap_knn returns for the
+ *   row once its own column is left out.  j == i gives 0; a j outside [0, n) is not dereferenced and gives -1.  out int32
+ *   [n][m].  Integers only; row i of out depends on row i of dist and of nbr_idx alone.
+ * pti_segment_row_sums: seg int32 DEVICE array of groups + 1 ascending offsets with seg[0] = 0 and seg[groups] = n (the
+ *   seg_a convention of pti_latent_group_stats), 1 <= groups <= 2048.  out[i][g] = sum_{j = seg[g]}^{seg[g+1]-1}
+ *   (double)dist[i][j], fp64 [n][groups] dense; the entries are converted as they are loaded and added in ONE order that
+ *   depends on the segment's length alone, so the bits of an entry depend on row i and that segment, not on n, groups or
+ *   the launch.  An empty segment gives 0.0.  The kernel clamps offsets to [0, n] and treats a segment that does not
+ *   ascend as empty: it never reads outside the row; the caller checks the table's ends.
+ * pti_projection_distances: y fp32 [n][d], the projection's rows (row stride ldy >= d in ELEMENTS), 1 <= n <= 8192,
+ *   1 <= d <= 8.  out[i][j] = (float)sqrt(sum_k ((double)y[i][k] - (double)y[j][k])^2), fp32 [n][n] with row stride
+ *   ldo >= n: formed in fp64 and rounded once, so two entries of a row are ordered as the true distances are unless they
+ *   round to the same fp32.  Symmetric bit for bit, zero diagonal.  (pti_latent_pairwise accumulates in fp32; for the
+ *   long latent rows that is the design, for a picture's coordinates the fp64 route is free.)
+ * One launch each on the caller's stream; no workspace, no atomics, no host synchronisation; bitwise reproducible.
+ * Refused before any launch: null pointers, n < 3 (pti_projection_distances: n < 1, d < 1), m < 1, groups < 1, a row
+ * stride below the row length, a misaligned buffer (PTI_EINVAL); n > 8192, m > 256, groups > 2048, d > 8 (PTI_EUNSUPPORTED). */
+int pti_neighbor_ranks(const float* dist, int64_t ldd, int n, const int32_t* nbr_idx, int m, int32_t* out, pti_stream_t s);
+int pti_segment_row_sums(const float* dist, int64_t ldd, int n, const int32_t* seg, int groups, double* out, pti_stream_t s);
+int pti_projection_distances(const float* y, int64_t ldy, int n, int d, float* out, int64_t ldo, pti_stream_t s);
 
 #ifdef __cplusplus
 }

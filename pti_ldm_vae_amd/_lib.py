@@ -195,6 +195,9 @@ SIGNATURES = {
     "pti_ksg_counts": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pti_mask_compare_ws_bytes": (_I64, [_I, _I, _I]),
     "pti_mask_compare": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _I64, _P]),
+    "pti_neighbor_ranks": (_I, [_P, _I64, _I, _P, _I, _P, _P]),
+    "pti_segment_row_sums": (_I, [_P, _I64, _I, _P, _I, _P, _P]),
+    "pti_projection_distances": (_I, [_P, _I64, _I, _I, _P, _I64, _P]),
 }
 
 _lib = None

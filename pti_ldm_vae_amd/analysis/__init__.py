@@ -1,10 +1,13 @@
 """Latent-space analysis of a trained VAE (reference ``src/pti_ldm_vae/analysis``): cached deterministic encodes, PCA /
 t-SNE / UMAP projections and per-patient distance statistics between two image groups, with the distance, statistics
-and Gram-matrix arithmetic on the device (``ops.latent_pairwise`` / ``ops.latent_group_stats``).  The reference's
+and Gram-matrix arithmetic on the device (``ops.latent_pairwise`` / ``ops.latent_group_stats``), and a quality report of a
+projection (``projection_quality``: trustworthiness, continuity, label separation).  The reference's
 image-comparison class (cv2, skimage, VGG) is not part of this package."""
 from .latent_cache import LatentCache
 from .latent_distance import latent_distance, latent_distance_cross, latent_distance_from_indices
 from .latent_space import (LatentSpaceAnalyzer, compute_distance_metrics, extract_patient_id_from_filename, load_image_paths)
+from .projection_quality import projection_quality
 
 __all__ = ["LatentCache", "LatentSpaceAnalyzer", "compute_distance_metrics", "extract_patient_id_from_filename",
-           "latent_distance", "latent_distance_cross", "latent_distance_from_indices", "load_image_paths"]
+           "latent_distance", "latent_distance_cross", "latent_distance_from_indices", "load_image_paths",
+           "projection_quality"]

@@ -503,6 +503,14 @@ class LatentSpaceAnalyzer:
                                  exploration_n_iter, early_exaggeration)
         return y.cpu().double().numpy()
 
+    # ---- projection quality ----
+    def projection_quality(self, latent_vectors, projection, *, neighbors=(5, 15, 40), labels=None) -> tuple[dict, dict]:
+        """How faithful ``projection`` ``[N, 2]`` is to ``latent_vectors`` ``[N, D]`` (the rows as given to the reduction,
+        before any PCA) and how separate the ``labels`` are in either space -> ``(report, per-point arrays)``:
+        ``analysis.projection_quality`` on this analyzer's device."""
+        from .projection_quality import projection_quality
+        return projection_quality(latent_vectors, projection, neighbors=neighbors, labels=labels, device=self.device)
+
     # ---- colours ----
     def create_patient_colormap(self, patient_ids: list[str]) -> tuple[dict[str, int], dict[str, str]]:
         """-> (patient -> index in sorted order, patient -> hex colour, cycling through ``PATIENT_PALETTE``)."""

@@ -12,6 +12,10 @@ the dentulous group is placed into that embedding, as the reference does; the de
 Outputs in ``--output-dir``: ``<method>_projection.png`` (matplotlib; ``.html`` through plotly when that fails),
 ``color_legend.txt`` with ``--color-by-patient``, and with two groups ``distance_metrics.txt``,
 ``exams_sorted_by_distance.txt`` and ``latents.npz`` (latents, ids, paths and projection of each group).
+``--quality [--quality-neighbors K ...]`` rates the projection, whichever method and backend made it
+(``analysis.projection_quality``: trustworthiness, continuity and neighbourhood preservation per ``K``, and how separate the
+groups and a patient's exams are in the latent space and in the picture) into ``projection_quality.json``,
+``projection_quality.npz`` and ``<method>_projection_quality.png``; without it nothing changes.
 
 Images are encoded deterministically in batches on the HIP engine; each image's latent is cached on disk in the
 reference's layout (``analysis.LatentCache``), so a second run on the same folders encodes nothing."""
@@ -27,13 +31,15 @@ from .analysis import LatentCache, LatentSpaceAnalyzer, load_image_paths
 
 
 class _Args(argparse.Namespace):
-    """The namespace ``parse_args`` fills.  ``--tsne-backend``, ``--umap-backend`` and ``--umap-fit-group`` live here as class
-    defaults and enter the instance only when they are given, so a command line without them parses to exactly the
-    attributes it always had."""
+    """The namespace ``parse_args`` fills.  ``--tsne-backend``, ``--umap-backend``, ``--umap-fit-group``, ``--quality`` and
+    ``--quality-neighbors`` live here as class defaults and enter the instance only when they are given, so a command line
+    without them parses to exactly the attributes it always had."""
 
     tsne_backend = "sklearn"
     umap_backend = "umap-learn"
     umap_fit_group = "all"
+    quality = False
+    quality_neighbors = (5, 15, 40)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -60,6 +66,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     parser.add_argument("--umap-fit-group", type=str, choices=["all", "edente"], default=argparse.SUPPRESS,
                         help="Rows UMAP is fitted on: all (both groups together; default) or edente (the edentulous group "
                              "alone, the dentulous group is then placed into its embedding; needs --umap-backend hip)")
+    parser.add_argument("--quality", action="store_true", default=argparse.SUPPRESS,
+                        help="Also rate the projection: trustworthiness, continuity, neighbourhood preservation and the "
+                             "separation of groups / patients in both spaces (projection_quality.json / .npz and "
+                             "<method>_projection_quality.png)")
+    parser.add_argument("--quality-neighbors", type=int, nargs="+", default=argparse.SUPPRESS, metavar="K",
+                        help="Neighbour counts of --quality (default: 5 15 40; each at most 255, those not below half the "
+                             "number of images are listed as excluded)")
     parser.add_argument("--seed", type=int, default=42, help="Random seed for reproducibility")
     parser.add_argument("--subtitle", type=str, default=None, help="Optional subtitle for the plot")
     parser.add_argument("--dpi", type=int, default=300, help="DPI for output PNG (default: 300)")
@@ -175,6 +188,72 @@ def save_projection_plot(groups: list, output_path: Path, title: str, subtitle: 
         return html_path
 
 
+def save_quality_plot(points: np.ndarray, values: np.ndarray, output_path: Path, title: str, dpi: int) -> Path:
+    """The projection's scatter coloured by a per-point value, with a colour bar."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    fig, ax = plt.subplots(figsize=(8, 7))
+    sc = ax.scatter(points[:, 0], points[:, 1], s=36, c=values, cmap="viridis", vmax=1.0, linewidths=0.0)
+    fig.colorbar(sc, ax=ax, label="local trustworthiness")
+    ax.set_xlabel("Dimension 1")
+    ax.set_ylabel("Dimension 2")
+    ax.set_title(title)
+    ax.grid(True, color="lightgray")
+    fig.savefig(output_path, dpi=dpi)
+    plt.close(fig)
+    return output_path
+
+
+def write_projection_quality(analyzer: LatentSpaceAnalyzer, groups: list, projected: list, method: str,
+                             args: argparse.Namespace, output_dir: Path) -> dict:
+    """``--quality``: rates the projection of all rows (both groups concatenated, also under ``--umap-fit-group edente``) and
+    writes ``projection_quality.json`` (byte-identical between two runs), ``projection_quality.npz`` (the per-point arrays,
+    ids and paths in the order of the projection) and ``<method>_projection_quality.png``.  -> the report."""
+    import json
+    latents = np.concatenate([g[0] for g in groups])
+    projection = np.concatenate([np.asarray(p) for p in projected])
+    ids = [i for g in groups for i in g[1]]
+    labels = {}
+    if len(groups) > 1:
+        labels["group"] = [g[3] for g in groups for _ in g[1]]
+    if len(set(ids)) < len(ids):                            # at least one patient with two or more rows
+        labels["patient"] = ids
+    neighbors = [int(k) for k in getattr(args, "quality_neighbors", _Args.quality_neighbors)]
+    try:
+        report, points = analyzer.projection_quality(latents, projection, neighbors=neighbors, labels=labels)
+    except ValueError as e:
+        raise SystemExit(f"analyze_static: --quality: {e}")
+    resolved = {k: getattr(args, k) for k in sorted(set(vars(args)) | {"tsne_backend", "umap_backend", "umap_fit_group"})}
+    resolved.update(quality=True, quality_neighbors=neighbors)
+    doc = {"method": method, "n": report["n"], "high_dims": report["high_dims"], "neighbors": report["neighbors"],
+           "excluded": {str(k): v for k, v in report["excluded"].items()}}
+    for key in ("trustworthiness", "continuity", "neighborhood_preservation"):
+        doc[key] = {str(k): v for k, v in report[key].items()}
+    doc["labels"] = {name: {key: ({str(k): v for k, v in val.items()} if isinstance(val, dict) else val)
+                            for key, val in entry.items()} for name, entry in report["labels"].items()}
+    doc["args"] = resolved
+    (output_dir / "projection_quality.json").write_text(json.dumps(doc, indent=2, allow_nan=False) + "\n")
+    np.savez(output_dir / "projection_quality.npz", ids=np.array(ids), paths=np.array([p for g in groups for p in g[2]]),
+             groups=np.array([g[3] for g in groups for _ in g[1]]), projection=projection,
+             neighbors=np.array(report["neighbors"], dtype=np.int64), **points)
+    for k in report["neighbors"]:
+        print(f"Projection quality k={k}: trustworthiness {report['trustworthiness'][k]:.4f}, continuity "
+              f"{report['continuity'][k]:.4f}, neighbourhood preservation {report['neighborhood_preservation'][k]:.4f}")
+    for k, reason in report["excluded"].items():
+        print(f"Projection quality k={k}: excluded ({reason})")
+    if report["neighbors"]:
+        k = max(report["neighbors"])
+        column = report["neighbors"].index(k)
+        title = {"umap": "UMAP", "tsne": "t-SNE", "pca": "PCA"}[method]
+        save_quality_plot(projection, points["trustworthiness_local"][:, column], output_dir / f"{method}_projection_quality.png",
+                          f"{title}: local trustworthiness (k = {k})", args.dpi)
+    else:
+        print("[WARN] no admitted neighbour count: the quality picture is not written")
+    print(f"✅ Projection quality saved: {output_dir / 'projection_quality.json'}")
+    return report
+
+
 def main(argv=None) -> None:
     from . import _lib
     from .utils.cli_common import init_device_and_seed, load_config_and_model
@@ -234,6 +313,8 @@ def main(argv=None) -> None:
         np.savez(output_dir / "latents.npz", **arrays)
         print(f"✅ Statistics saved to {output_dir}/distance_metrics.txt")
         print(f"✅ Sorted exams saved to {output_dir}/exams_sorted_by_distance.txt")
+    if getattr(args, "quality", False):
+        write_projection_quality(analyzer, groups, projected, method, args, output_dir)
     print("✅ Analysis complete!")
 
 

@@ -1593,6 +1593,94 @@ def ksg_counts(z, attrs, k, *, out=None):
     return eps, nx, ny
 
 
+# ---- projection quality (csrc/projection_quality.hip; include/pti_vae.h "projection quality") --------------------------
+NEIGHBOR_RANKS_MAX_N, NEIGHBOR_RANKS_MAX_M, SEGMENT_ROW_SUMS_MAX_G = 8192, 256, 2048
+
+
+PROJECTION_MAX_COLS = 8
+
+
+def projection_distances(y, *, out=None):
+    """Euclidean distances between the rows of a PROJECTION ``y`` [n, d], d <= 8 (``pti_projection_distances``) -> fp32
+    ``[n, n]``: differences, squares, sum and root in fp64, rounded to fp32 once.  Two entries of a row are therefore ordered
+    as the true distances are unless they round to the same fp32 (``latent_pairwise`` accumulates in fp32 and orders
+    distances a few units in the last place apart by its rounding).  Symmetric bit for bit with a zero diagonal.  A
+    row-strided ``y`` and an ``out`` view with a row stride are used in place.  1 <= n <= 8192.  Runs on the current stream,
+    no host sync."""
+    y = _rows(y, "projection_distances: y")
+    n, d = y.shape
+    if not (1 <= n <= NEIGHBOR_RANKS_MAX_N and 1 <= d <= PROJECTION_MAX_COLS):
+        raise ValueError(f"projection_distances: unsupported shape {tuple(y.shape)} (1 <= n <= {NEIGHBOR_RANKS_MAX_N}, "
+                         f"1 <= d <= {PROJECTION_MAX_COLS})")
+    out = _latent_out(out, (n, n), y, "projection_distances")
+    L.check(L.lib().pti_projection_distances(_ptr(y), y.stride(0), n, d, _ptr(out), out.stride(0), _stream()),
+            "pti_projection_distances")
+    return out
+
+
+def neighbor_ranks(dist, nbr_idx, *, out=None):
+    """The rank, within row ``i`` of the fp32 distance matrix ``dist`` [n, n], of every listed neighbour ``nbr_idx[i, c]``
+    (``pti_neighbor_ranks``) -> int32 ``[n, m]``: ``1 + #{l != i : key(i, l) < key(i, j)}`` under ``umap_knn``'s order
+    (distance, then column; -0 is 0), so "rank <= k" is the set ``umap_knn`` returns once the diagonal is left out.  An
+    entry equal to its own row gives 0, an index outside ``[0, n)`` gives -1.  ``dist`` is used in place (a row stride is
+    allowed); ``nbr_idx`` int32 ``[n, m]`` contiguous.  3 <= n <= 8192, 1 <= m <= 256.  Integers only: exact; a row of the
+    result depends on that row of ``dist`` and of ``nbr_idx`` alone.  Runs on the current stream, no host sync."""
+    who = "neighbor_ranks"
+    dist = _tsne_matrix(dist, f"{who}: dist")
+    if not isinstance(nbr_idx, torch.Tensor):
+        raise ValueError(f"{who}: nbr_idx: expected a CUDA(HIP) tensor")
+    _chk(nbr_idx, I32, f"{who}: nbr_idx", 2)
+    n, m = dist.shape[0], nbr_idx.shape[1]
+    if nbr_idx.shape[0] != n or nbr_idx.device != dist.device:
+        raise ValueError(f"{who}: nbr_idx must be [{n}, m] on {dist.device}, got {tuple(nbr_idx.shape)} on {nbr_idx.device}")
+    if not (3 <= n <= NEIGHBOR_RANKS_MAX_N and 1 <= m <= NEIGHBOR_RANKS_MAX_M):
+        raise ValueError(f"{who}: unsupported shape dist {tuple(dist.shape)} nbr_idx {tuple(nbr_idx.shape)} "
+                         f"(3 <= n <= {NEIGHBOR_RANKS_MAX_N}, 1 <= m <= {NEIGHBOR_RANKS_MAX_M})")
+    out = _out(out, (n, m), I32, dist.device, f"{who}: out")
+    L.check(L.lib().pti_neighbor_ranks(_ptr(dist), dist.stride(0), n, _ptr(nbr_idx), m, _ptr(out), _stream()),
+            "pti_neighbor_ranks")
+    return out
+
+
+def segment_row_sums(dist, seg, *, out=None):
+    """Per-segment sums of every row of the fp32 distance matrix ``dist`` [n, n] (``pti_segment_row_sums``) -> fp64
+    ``[n, G]``: ``out[i, g] = sum_{j = seg[g]}^{seg[g+1]-1} (double)dist[i, j]``.  ``seg``: the ``G + 1`` ascending int32
+    offsets with ``seg[0] = 0`` and ``seg[G] = n`` (``latent_group_stats``'s ``seg_a`` convention), as a host sequence / CPU
+    tensor (checked on the host, copied to the device) or an int32 device vector (checked through one read-back, the only
+    host synchronisation here).  The fp32 values are widened as they are loaded -- no fp64 copy of the matrix -- and added in
+    one order that depends on the segment's length alone: the bits of an entry depend on its row and its segment, not on
+    ``n``, ``G`` or the launch.  An empty segment gives 0.0.  3 <= n <= 8192, 1 <= G <= 2048.  Runs on the current stream."""
+    who = "segment_row_sums"
+    dist = _tsne_matrix(dist, f"{who}: dist")
+    n = dist.shape[0]
+    if isinstance(seg, torch.Tensor):
+        if seg.dtype != I32:
+            raise TypeError(f"{who}: seg must be int32, got {seg.dtype}")
+        if seg.dim() != 1 or not seg.is_contiguous():
+            raise ValueError(f"{who}: seg must be a contiguous vector of G + 1 offsets")
+        if seg.is_cuda and seg.device != dist.device:
+            raise ValueError(f"{who}: seg must be on {dist.device}")
+        host = seg.tolist()
+    else:
+        host = [int(v) for v in seg]
+        seg = torch.tensor(host, dtype=I32)
+    g = len(host) - 1
+    if not (3 <= n <= NEIGHBOR_RANKS_MAX_N and 1 <= g <= SEGMENT_ROW_SUMS_MAX_G):
+        raise ValueError(f"{who}: unsupported shape dist {tuple(dist.shape)} with {g} segments "
+                         f"(3 <= n <= {NEIGHBOR_RANKS_MAX_N}, 1 <= G <= {SEGMENT_ROW_SUMS_MAX_G})")
+    if host[0] != 0 or host[-1] != n or any(b < a for a, b in zip(host, host[1:])):
+        raise ValueError(f"{who}: seg must ascend from 0 to n = {n}, got {host[0]} .. {host[-1]}")
+    if not seg.is_cuda:
+        seg = seg.to(dist.device)
+    if out is None:
+        out = torch.empty((n, g), dtype=torch.float64, device=dist.device)
+    else:
+        out = _out(out, (n, g), torch.float64, dist.device, f"{who}: out")
+    L.check(L.lib().pti_segment_row_sums(_ptr(dist), dist.stride(0), n, _ptr(seg), g, _ptr(out), _stream()),
+            "pti_segment_row_sums")
+    return out
+
+
 # ---- PatchDiscriminator passes (csrc/discriminator.hip; include/pti_vae.h "PatchDiscriminator") -----------------------
 def pd_out_hw(h, w, stride):
     return (h + 2 - 4) // stride + 1, (w + 2 - 4) // stride + 1
