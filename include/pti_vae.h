@@ -45,7 +45,8 @@ typedef void* pti_stream_t; /* hipStream_t */
                                Still 5: pti_display_planes appended in the same way.
                                Still 5: pti_mask_compare / pti_mask_compare_ws_bytes appended in the same way.
                                Still 5: pti_neighbor_ranks / pti_segment_row_sums / pti_projection_distances appended in the
-                               same way. */
+                               same way.
+                               Still 5: pti_full_ranks / pti_coranking_fold / pti_shepard_fold appended in the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -839,6 +840,32 @@ int pti_mask_compare(const float* gt, const float* pred, int n, int h, int w, fl
 int pti_neighbor_ranks(const float* dist, int64_t ldd, int n, const int32_t* nbr_idx, int m, int32_t* out, pti_stream_t s);
 int pti_segment_row_sums(const float* dist, int64_t ldd, int n, const int32_t* seg, int groups, double* out, pti_stream_t s);
 int pti_projection_distances(const float* y, int64_t ldy, int n, int d, float* out, int64_t ldo, pti_stream_t s);
+
+/* ---- co-ranking curves and the Shepard figure of a projection (Lee & Verleysen's Q_NX / B_NX / R_NX / LCMC; Kruskal's
+ *      stress-1; csrc/coranking.hip) ----
+ * 4 <= n <= 8192 columns everywhere; row strides in ELEMENTS, at least n; matrices are used in place.
+ * pti_full_ranks: dist fp32 [m][n] holds rows row0 .. row0 + m - 1 of an n-column distance matrix (0 <= row0, row0 + m <= n).
+ *     out[r][j] = 1 + #{ l != i : key(i, l) < key(i, j) },  i = row0 + r,  out[r][i] = 0,
+ *   with pti_neighbor_ranks' key (the fp32 bits, -0 taken as 0, above the column): every row of out is a permutation of
+ *   0 .. n - 1.  out int16 [m][n], row stride ldo, any 2-byte alignment.  One workgroup per row sorts the row's keys in LDS.
+ * pti_coranking_fold: rank_high / rank_low int16 [m][n], two such tables of the same rows.  For every entry with BOTH ranks
+ *   in [1, n - 1] (anything else, the own column's 0 included, is skipped and never used as an index), with b = max of the
+ *   two: hist[0][b] += 1 where they are equal, hist[1][b] += 1 where rank_low < rank_high (an intrusion), hist[2][b] += 1
+ *   where rank_high < rank_low (an extrusion); hist uint32 [3][n] dense, ADDED to (the caller zeroes it; calls over row
+ *   blocks compose).  sqdiff[r] = the sum over the same entries of (rank_high - rank_low)^2, int64 [m], written.
+ * pti_shepard_fold: dist_high / dist_low fp32 [n][n].  sums[i] = { sum d_high^2, sum d_low^2, sum d_high d_low } over
+ *   j != i, fp64 [n][3] dense, written: products formed in fp64 (exact) and added in ONE order that depends on n alone.
+ *   hist[bh][bl] += 1 for every such pair, bh = (int)(d_high * scale[0]) and bl = (int)(d_low * scale[1]) in fp32, each
+ *   clamped to [0, bins - 1] (+inf and NaN: the last bin); scale: a DEVICE pair of fp32; 2 <= bins <= 128; hist uint32
+ *   [bins][bins] dense, ADDED to.
+ * One launch each on the caller's stream; no workspace; integer atomics only, so every output is bitwise reproducible.
+ * Refused before any launch: null pointers, n < 4, m < 1, a row range outside the matrix, a row stride below n, bins < 2,
+ * a misaligned buffer (PTI_EINVAL); n > 8192, bins > 128 (PTI_EUNSUPPORTED). */
+int pti_full_ranks(const float* dist, int64_t ldd, int m, int n, int row0, int16_t* out, int64_t ldo, pti_stream_t s);
+int pti_coranking_fold(const int16_t* rank_high, int64_t ldh, const int16_t* rank_low, int64_t ldl, int m, int n, uint32_t* hist,
+                       int64_t* sqdiff, pti_stream_t s);
+int pti_shepard_fold(const float* dist_high, int64_t ldh, const float* dist_low, int64_t ldl, int n, const float* scale, int bins,
+                     double* sums, uint32_t* hist, pti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -198,6 +198,9 @@ SIGNATURES = {
     "pti_neighbor_ranks": (_I, [_P, _I64, _I, _P, _I, _P, _P]),
     "pti_segment_row_sums": (_I, [_P, _I64, _I, _P, _I, _P, _P]),
     "pti_projection_distances": (_I, [_P, _I64, _I, _I, _P, _I64, _P]),
+    "pti_full_ranks": (_I, [_P, _I64, _I, _I, _I, _P, _I64, _P]),
+    "pti_coranking_fold": (_I, [_P, _I64, _P, _I64, _I, _I, _P, _P, _P]),
+    "pti_shepard_fold": (_I, [_P, _I64, _P, _I64, _I, _P, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -511,6 +511,13 @@ class LatentSpaceAnalyzer:
         from .projection_quality import projection_quality
         return projection_quality(latent_vectors, projection, neighbors=neighbors, labels=labels, device=self.device)
 
+    def projection_curves(self, latent_vectors, projection, bins: int = 64) -> tuple[dict, dict]:
+        """At which scale ``projection`` ``[N, 2]`` can be believed: the co-ranking curves ``Q_NX`` / ``B_NX`` / ``R_NX`` /
+        ``LCMC`` for every neighbourhood size and the Shepard figure -> ``(report, arrays)``:
+        ``analysis.coranking_curves`` on this analyzer's device."""
+        from .coranking import coranking_curves
+        return coranking_curves(latent_vectors, projection, bins=bins, device=self.device)
+
     # ---- colours ----
     def create_patient_colormap(self, patient_ids: list[str]) -> tuple[dict[str, int], dict[str, str]]:
         """-> (patient -> index in sorted order, patient -> hex colour, cycling through ``PATIENT_PALETTE``)."""

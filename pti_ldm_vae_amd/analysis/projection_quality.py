@@ -22,22 +22,22 @@ import torch
 MAX_ROWS, MIN_ROWS, MAX_NEIGHBORS, MAX_CLASSES = 8192, 4, 255, 2048
 
 
-def _device_rows(x, name: str, device) -> torch.Tensor:
+def _device_rows(x, name: str, device, who: str = "projection_quality") -> torch.Tensor:
     """-> fp32 device matrix; a non-finite value is refused (for a device tensor through one read-back)."""
     if isinstance(x, torch.Tensor):
         if x.dim() != 2:
-            raise ValueError(f"projection_quality: {name}: expected a matrix, got {tuple(x.shape)}")
+            raise ValueError(f"{who}: {name}: expected a matrix, got {tuple(x.shape)}")
         t = x.to(device, torch.float32)
         finite = bool(torch.isfinite(t).all())
     else:
         a = np.asarray(x)
         if a.ndim != 2:
-            raise ValueError(f"projection_quality: {name}: expected a matrix, got {a.shape}")
+            raise ValueError(f"{who}: {name}: expected a matrix, got {a.shape}")
         a = np.ascontiguousarray(a, dtype=np.float32)
         finite = bool(np.isfinite(a).all())
         t = torch.from_numpy(a).to(device)
     if not finite:
-        raise ValueError(f"projection_quality: {name} holds a non-finite value")
+        raise ValueError(f"{who}: {name} holds a non-finite value")
     return t
 
 

@@ -16,6 +16,10 @@ Outputs in ``--output-dir``: ``<method>_projection.png`` (matplotlib; ``.html`` 
 (``analysis.projection_quality``: trustworthiness, continuity and neighbourhood preservation per ``K``, and how separate the
 groups and a patient's exams are in the latent space and in the picture) into ``projection_quality.json``,
 ``projection_quality.npz`` and ``<method>_projection_quality.png``; without it nothing changes.
+``--quality-curves [--quality-bins B]`` says at which scale the picture can be believed (``analysis.coranking_curves``: the
+co-ranking curves Q_NX, B_NX, R_NX for every neighbourhood size, their scale-free score, the rank correlation per point and
+a Shepard diagram with its stress) into ``projection_curves.json``, ``projection_curves.npz`` and
+``<method>_projection_curves.png``; it is independent of ``--quality``, and without it nothing changes either.
 
 Images are encoded deterministically in batches on the HIP engine; each image's latent is cached on disk in the
 reference's layout (``analysis.LatentCache``), so a second run on the same folders encodes nothing."""
@@ -31,15 +35,17 @@ from .analysis import LatentCache, LatentSpaceAnalyzer, load_image_paths
 
 
 class _Args(argparse.Namespace):
-    """The namespace ``parse_args`` fills.  ``--tsne-backend``, ``--umap-backend``, ``--umap-fit-group``, ``--quality`` and
-    ``--quality-neighbors`` live here as class defaults and enter the instance only when they are given, so a command line
-    without them parses to exactly the attributes it always had."""
+    """The namespace ``parse_args`` fills.  ``--tsne-backend``, ``--umap-backend``, ``--umap-fit-group``, ``--quality``,
+    ``--quality-neighbors``, ``--quality-curves`` and ``--quality-bins`` live here as class defaults and enter the instance
+    only when they are given, so a command line without them parses to exactly the attributes it always had."""
 
     tsne_backend = "sklearn"
     umap_backend = "umap-learn"
     umap_fit_group = "all"
     quality = False
     quality_neighbors = (5, 15, 40)
+    quality_curves = False
+    quality_bins = 64
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -73,6 +79,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     parser.add_argument("--quality-neighbors", type=int, nargs="+", default=argparse.SUPPRESS, metavar="K",
                         help="Neighbour counts of --quality (default: 5 15 40; each at most 255, those not below half the "
                              "number of images are listed as excluded)")
+    parser.add_argument("--quality-curves", action="store_true", default=argparse.SUPPRESS,
+                        help="Also say at which scale the projection can be believed: the co-ranking curves Q_NX, B_NX, R_NX "
+                             "for every neighbourhood size, AUC_logK, the rank correlation and a Shepard diagram with its "
+                             "stress (projection_curves.json / .npz and <method>_projection_curves.png)")
+    parser.add_argument("--quality-bins", type=int, default=argparse.SUPPRESS, metavar="B",
+                        help="Bins per axis of the Shepard diagram of --quality-curves (default: 64; 2 .. 128)")
     parser.add_argument("--seed", type=int, default=42, help="Random seed for reproducibility")
     parser.add_argument("--subtitle", type=str, default=None, help="Optional subtitle for the plot")
     parser.add_argument("--dpi", type=int, default=300, help="DPI for output PNG (default: 300)")
@@ -254,6 +266,75 @@ def write_projection_quality(analyzer: LatentSpaceAnalyzer, groups: list, projec
     return report
 
 
+def save_curves_plot(report: dict, arrays: dict, output_path: Path, title: str, dpi: int) -> Path:
+    """Three panels: ``Q_NX`` and ``R_NX`` against ``K`` on a log axis with ``K_max`` marked, ``B_NX``, the Shepard heat map."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    n = report["n"]
+    k = np.arange(1, n)
+    fig, (left, mid, right) = plt.subplots(1, 3, figsize=(18, 5.5))
+    left.semilogx(k, arrays["Q_NX"], label="Q_NX")
+    left.semilogx(k[:-1], arrays["R_NX"], label=f"R_NX (AUC_logK = {report['auc_logk_rnx']:.3f})")
+    left.axvline(report["k_max"], color="gray", linestyle="--", label=f"K_max = {report['k_max']}")
+    left.set_xlabel("K")
+    left.set_ylim(min(0.0, float(arrays["R_NX"].min())), 1.0)
+    left.set_title(title)
+    left.legend(loc="best")
+    mid.semilogx(k, arrays["B_NX"], color="#d62728")
+    mid.axhline(0.0, color="gray", linewidth=0.8)
+    mid.set_xlabel("K")
+    mid.set_title("B_NX (above 0: extrusive, below 0: intrusive)")
+    for ax in (left, mid):
+        ax.grid(True, color="lightgray")
+    eh, el = arrays["shepard_edges_high"], arrays["shepard_edges_low"]
+    if eh[-1] > 0 and el[-1] > 0:
+        mesh = right.pcolormesh(eh, el, np.log1p(arrays["shepard_hist"].T.astype(np.float64)), cmap="viridis")
+        fig.colorbar(mesh, ax=right, label="log(1 + pairs)")
+    right.set_xlabel("latent distance")
+    right.set_ylabel("projection distance")
+    right.set_title("Shepard diagram" + ("" if report["stress"] is None else f" (stress {report['stress']:.3f})"))
+    fig.savefig(output_path, dpi=dpi)
+    plt.close(fig)
+    return output_path
+
+
+def write_projection_curves(analyzer: LatentSpaceAnalyzer, groups: list, projected: list, method: str,
+                            args: argparse.Namespace, output_dir: Path) -> dict:
+    """``--quality-curves``: the co-ranking curves and the Shepard figure of the projection of all rows (both groups
+    concatenated, also under ``--umap-fit-group edente``) -> ``projection_curves.json`` (byte-identical between two runs; the
+    curves at ``K`` = 1, 2, 5, 10, ... only), ``projection_curves.npz`` (the full curves, histograms and per-point values, ids
+    and paths in the order of the projection) and ``<method>_projection_curves.png``.  -> the report."""
+    import json
+
+    from .analysis.coranking import curve_samples
+    latents = np.concatenate([g[0] for g in groups])
+    projection = np.concatenate([np.asarray(p) for p in projected])
+    bins = int(getattr(args, "quality_bins", _Args.quality_bins))
+    try:
+        report, arrays = analyzer.projection_curves(latents, projection, bins=bins)
+    except ValueError as e:
+        raise SystemExit(f"analyze_static: --quality-curves: {e}")
+    ks = curve_samples(report["n"])
+    doc = {"method": method}
+    doc.update(report)
+    doc["K"] = ks
+    for key in ("Q_NX", "B_NX", "R_NX"):
+        doc[key] = {str(k): float(arrays[key][k - 1]) for k in ks if k - 1 < len(arrays[key])}
+    (output_dir / "projection_curves.json").write_text(json.dumps(doc, indent=2, allow_nan=False) + "\n")
+    np.savez(output_dir / "projection_curves.npz", ids=np.array([i for g in groups for i in g[1]]),
+             paths=np.array([p for g in groups for p in g[2]]), groups=np.array([g[3] for g in groups for _ in g[1]]),
+             projection=projection, **arrays)
+    title = {"umap": "UMAP", "tsne": "t-SNE", "pca": "PCA"}[method]
+    save_curves_plot(report, arrays, output_dir / f"{method}_projection_curves.png", f"{title}: co-ranking curves", args.dpi)
+    tail = "" if report["q_global"] is None else f", Q_global {report['q_global']:.4f}"
+    stress = "undefined" if report["stress"] is None else f"{report['stress']:.4f}"
+    print(f"Projection curves: AUC_logK(R_NX) {report['auc_logk_rnx']:.4f}, K_max {report['k_max']}, Q_local "
+          f"{report['q_local']:.4f}{tail}, rank correlation {report['rank_correlation']:.4f}, stress {stress}")
+    print(f"✅ Projection curves saved: {output_dir / 'projection_curves.json'}")
+    return report
+
+
 def main(argv=None) -> None:
     from . import _lib
     from .utils.cli_common import init_device_and_seed, load_config_and_model
@@ -315,6 +396,8 @@ def main(argv=None) -> None:
         print(f"✅ Sorted exams saved to {output_dir}/exams_sorted_by_distance.txt")
     if getattr(args, "quality", False):
         write_projection_quality(analyzer, groups, projected, method, args, output_dir)
+    if getattr(args, "quality_curves", False):
+        write_projection_curves(analyzer, groups, projected, method, args, output_dir)
     print("✅ Analysis complete!")
 
 

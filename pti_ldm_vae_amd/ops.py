@@ -1681,6 +1681,105 @@ def segment_row_sums(dist, seg, *, out=None):
     return out
 
 
+# ---- co-ranking curves and the Shepard figure (csrc/coranking.hip; include/pti_vae.h "co-ranking curves") --------------
+CORANKING_MIN_N, CORANKING_MAX_N, SHEPARD_MIN_BINS, SHEPARD_MAX_BINS = 4, 8192, 2, 128
+I16 = torch.int16
+
+
+def _coranking_rows(t, dtype, name):
+    """A device matrix [m, n] of ``dtype`` with dense rows and 4 <= n <= 8192, 1 <= m <= n, used in place."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise ValueError(f"{name}: expected an [m, n] matrix with dense rows, got {tuple(t.shape)}")
+    m, n = t.shape
+    if not (CORANKING_MIN_N <= n <= CORANKING_MAX_N and 1 <= m <= n):
+        raise ValueError(f"{name}: unsupported shape {tuple(t.shape)} ({CORANKING_MIN_N} <= n <= {CORANKING_MAX_N} columns, "
+                         f"1 <= m <= n rows)")
+    return t
+
+
+def full_ranks(dist, row_offset=0, *, out=None):
+    """The rank of EVERY column within every row of the fp32 distance rows ``dist`` [m, n] (``pti_full_ranks``) -> int16
+    ``[m, n]``.  ``dist`` holds rows ``row_offset .. row_offset + m - 1`` of an ``n``-column matrix (the whole matrix when it
+    is square and ``row_offset`` is 0): ``out[r, j] = 1 + #{l != i : key(i, l) < key(i, j)}`` with ``i = row_offset + r``
+    under ``neighbor_ranks``' order (distance, then column; -0 is 0) and 0 at the row's own column, so a row is a
+    permutation of ``0 .. n - 1`` and ``full_ranks(d).gather(1, idx)`` is ``neighbor_ranks(d, idx)``.  One workgroup sorts a
+    row's 64-bit keys in LDS.  ``dist`` and an ``out`` view with a row stride are used in place.  4 <= n <= 8192.
+    Comparisons only: exact.  Runs on the current stream, no host sync."""
+    who = "full_ranks"
+    dist = _coranking_rows(dist, F32, f"{who}: dist")
+    m, n = dist.shape
+    row_offset = int(row_offset)
+    if not 0 <= row_offset <= n - m:
+        raise ValueError(f"{who}: rows {row_offset} .. {row_offset + m - 1} are outside the matrix of {n} rows")
+    if out is None:
+        out = torch.empty((m, n), dtype=I16, device=dist.device)
+    else:
+        _coranking_rows(out, I16, f"{who}: out")
+        if tuple(out.shape) != (m, n) or out.device != dist.device:
+            raise ValueError(f"{who}: out must be [{m}, {n}] on {dist.device}")
+    L.check(L.lib().pti_full_ranks(_ptr(dist), dist.stride(0), m, n, row_offset, _ptr(out), out.stride(0), _stream()),
+            "pti_full_ranks")
+    return out
+
+
+def coranking_fold(rank_high, rank_low, hist=None):
+    """The co-ranking histograms of two int16 rank tables ``[m, n]`` of the same rows (``pti_coranking_fold``) ->
+    ``(hist, sqdiff)``.  ``hist`` uint32-valued int32 ``[3, n]``: for every entry with both ranks in ``[1, n - 1]``, bin
+    ``max(rank_high, rank_low)`` of row 0 (equal ranks), 1 (``rank_low < rank_high``: an intrusion) or 2 (an extrusion)
+    is raised; anything else -- the own column's 0, a foreign value -- is skipped.  A ``hist`` handed in is ADDED to, so
+    calls over row blocks compose; without one a zeroed table is made.  ``sqdiff`` int64 ``[m]``: the row's sum of
+    ``(rank_high - rank_low)^2``.  Integer atomics only: exact and independent of scheduling.  Current stream, no host sync."""
+    who = "coranking_fold"
+    rank_high = _coranking_rows(rank_high, I16, f"{who}: rank_high")
+    rank_low = _coranking_rows(rank_low, I16, f"{who}: rank_low")
+    m, n = rank_high.shape
+    if tuple(rank_low.shape) != (m, n) or rank_low.device != rank_high.device:
+        raise ValueError(f"{who}: rank_low must be [{m}, {n}] on {rank_high.device}, got {tuple(rank_low.shape)}")
+    if hist is None:
+        hist = torch.zeros((3, n), dtype=I32, device=rank_high.device)
+    else:
+        hist = _out(hist, (3, n), I32, rank_high.device, f"{who}: hist")
+    sqdiff = torch.empty((m,), dtype=torch.int64, device=rank_high.device)
+    L.check(L.lib().pti_coranking_fold(_ptr(rank_high), rank_high.stride(0), _ptr(rank_low), rank_low.stride(0), m, n,
+                                       _ptr(hist), _ptr(sqdiff), _stream()), "pti_coranking_fold")
+    return hist, sqdiff
+
+
+def shepard_fold(dist_high, dist_low, bins=64, *, hist=None):
+    """The Shepard figure's raw material from two fp32 distance matrices ``[n, n]`` (``pti_shepard_fold``) ->
+    ``(sums, hist, scale)``.  ``sums`` fp64 ``[n, 3]``: per row the sums of ``d_high^2``, ``d_low^2`` and ``d_high d_low``
+    over the other columns, the products exact in fp64, added in one fixed order (the bits depend on the row and ``n``).
+    ``hist`` int32 ``[bins, bins]``: the count of ordered pairs in cell ``(min(bins - 1, int(d_high * scale[0])),
+    min(bins - 1, int(d_low * scale[1])))``, products in fp32; ``+inf`` goes to the last bin; a ``hist`` handed in is ADDED
+    to.  ``scale`` fp32 device pair: ``bins / (largest finite entry)`` of each matrix, 0 where that entry is 0 -- formed here
+    by torch, since the library's own division is not correctly rounded; bin ``b`` covers ``[b / scale, (b + 1) / scale)``.
+    4 <= n <= 8192, 2 <= bins <= 128.  Runs on the current stream, no host sync."""
+    who = "shepard_fold"
+    dist_high, dist_low = _tsne_matrix(dist_high, f"{who}: dist_high"), _tsne_matrix(dist_low, f"{who}: dist_low")
+    n, bins = dist_high.shape[0], int(bins)
+    if tuple(dist_low.shape) != (n, n) or dist_low.device != dist_high.device:
+        raise ValueError(f"{who}: dist_low must be [{n}, {n}] on {dist_high.device}, got {tuple(dist_low.shape)}")
+    if not (CORANKING_MIN_N <= n <= CORANKING_MAX_N and SHEPARD_MIN_BINS <= bins <= SHEPARD_MAX_BINS):
+        raise ValueError(f"{who}: unsupported shape n = {n}, bins = {bins} ({CORANKING_MIN_N} <= n <= {CORANKING_MAX_N}, "
+                         f"{SHEPARD_MIN_BINS} <= bins <= {SHEPARD_MAX_BINS})")
+    top = torch.stack([torch.where(torch.isfinite(d), d, torch.zeros((), dtype=F32, device=d.device)).max()
+                       for d in (dist_high, dist_low)])
+    # a tensor over a tensor: one correctly rounded division (a Python number over a tensor is reciprocal-then-multiply)
+    scale = torch.where(top > 0, torch.full_like(top, float(bins)) / top, torch.zeros_like(top)).contiguous()
+    if hist is None:
+        hist = torch.zeros((bins, bins), dtype=I32, device=dist_high.device)
+    else:
+        hist = _out(hist, (bins, bins), I32, dist_high.device, f"{who}: hist")
+    sums = torch.empty((n, 3), dtype=torch.float64, device=dist_high.device)
+    L.check(L.lib().pti_shepard_fold(_ptr(dist_high), dist_high.stride(0), _ptr(dist_low), dist_low.stride(0), n, _ptr(scale),
+                                     bins, _ptr(sums), _ptr(hist), _stream()), "pti_shepard_fold")
+    return sums, hist, scale
+
+
 # ---- PatchDiscriminator passes (csrc/discriminator.hip; include/pti_vae.h "PatchDiscriminator") -----------------------
 def pd_out_hw(h, w, stride):
     return (h + 2 - 4) // stride + 1, (w + 2 - 4) // stride + 1
