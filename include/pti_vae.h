@@ -46,7 +46,9 @@ typedef void* pti_stream_t; /* hipStream_t */
                                Still 5: pti_mask_compare / pti_mask_compare_ws_bytes appended in the same way.
                                Still 5: pti_neighbor_ranks / pti_segment_row_sums / pti_projection_distances appended in the
                                same way.
-                               Still 5: pti_full_ranks / pti_coranking_fold / pti_shepard_fold appended in the same way. */
+                               Still 5: pti_full_ranks / pti_coranking_fold / pti_shepard_fold appended in the same way.
+                               Still 5: pti_mask_moments (+ its _ws_bytes) / pti_warp_cubic / pti_align_bottom appended in
+                               the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -866,6 +868,65 @@ int pti_coranking_fold(const int16_t* rank_high, int64_t ldh, const int16_t* ran
                        int64_t* sqdiff, pti_stream_t s);
 int pti_shepard_fold(const float* dist_high, int64_t ldh, const float* dist_low, int64_t ldl, int n, const float* scale, int bins,
                      double* sums, uint32_t* hist, pti_stream_t s);
+
+/* ---- pair registration: straighten both sides of a pair, then align the prediction (reference
+ *      src/pti_ldm_vae/analysis/metrics.py:229-310: straighten_image, align_images_by_bottom_20_center; appended to
+ *      csrc/mask_compare.hip) ----
+ * G, R, K(.), F(.), the threshold t and the shape limits are those of "shape comparison" above; x is the column, y the row
+ * (y points down); all images of a call have one shape h x w.
+ * 1. Cleaned prediction: c = pred where P = F(K(R)), else 0.0f  (the reference's prediction * (mask > 0)).
+ * 2. Orientation, per side: the region is F(K(G)) on side 0 (ground truth) and P on side 1 (prediction).  Its six raw moments
+ *    m00, m10, m01, m20, m11, m02 are the int64 sums of 1, x, y, x^2, x y, y^2 over the region (exact), and
+ *      A = m00 m20 - m10^2,  B = m00 m11 - m10 m01,  C = m00 m02 - m01^2        (int64; they fit in 61 bits at 1024 x 1024).
+ *    B == 0 (decided on the integers): beta = 0 when C >= A, else beta = +pi/2 with cos beta = 0.0 and sin beta = 1.0 EXACTLY
+ *    -- an upright, mirror-symmetric or round object is not rotated at all.  Otherwise theta = atan2((double)(2 B),
+ *    (double)(A - C)) / 2 and beta = theta - pi/2 when theta > 0, else theta + pi/2: the rotation of least magnitude that makes
+ *    the major axis vertical.  An empty region has m00 = 0 and asks for no rotation (beta = 0, cos = 1, sin = 0); the caller
+ *    skips such a pair.  (The reference fits an ellipse to the largest outer contour's points: a deliberate difference.)
+ * 3. Rotation about cx = w / 2, cy = h / 2 (integer division).  Output pixel (x, y) takes the source point
+ *      sx = (cx + cos beta (x - cx)) - sin beta (y - cy),     sy = (cy + sin beta (x - cx)) + cos beta (y - cy)
+ *    in fp64, associated as written (a product may be fused with the sum that follows it).  fx = floor(sx),
+ *    tx = (float)(sx - fx), likewise y.  The output is the 4 x 4 cubic convolution over source columns fx - 1 .. fx + 2 and rows
+ *    fy - 1 .. fy + 2, indices clamped to the image (replicate border), with Keys' weights for a = -0.75 in fp32:
+ *      w0 = ((a (t + 1) - 5 a)(t + 1) + 8 a)(t + 1) - 4 a,   w1 = ((a + 2) t - (a + 3)) t^2 + 1,
+ *      w2 = w1 of 1 - t,                                     w3 = ((1 - w0) - w1) - w2,
+ *    a row is ((w0 v0 + w1 v1) + w2 v2) + w3 v3 over its columns, the pixel the same chain over the four rows; fp32, never
+ *    re-associated, multiply-adds possibly fused.  At t = 0 the weights are exactly 0, 1, 0, 0: with beta = 0 (or a quarter
+ *    turn's exact coefficients) the output is a copy of the source pixels, bit for bit but for a -0.0f, which comes out as
+ *    +0.0f.  The WHOLE image is rotated (gt itself, and c), not only the kept component.
+ * 4. Alignment: the rows used are the last h / 5.  In the rotated ground truth and the rotated prediction the mask is
+ *    pixel != 0; centre = (sum of the columns of the set pixels) / (their count), integer division; shift = centre_gt -
+ *    centre_pred; aligned[y][x] = rotated_pred[y][x - shift], 0.0f where x - shift leaves the row.
+ *
+ * pti_mask_moments: gt, pred fp32 [n][h][w] dense and finite -> cleaned fp32 [n][h][w] (rule 1),
+ *   moments int64 [n][2][PTI_MASK_MOMENTS_COLUMNS], side 0 = ground truth, side 1 = prediction, the columns
+ *      0 m00  1 m10  2 m01  3 m20  4 m11  5 m02  6 A  7 B  8 C  9 status (0, or 1 when a label-following loop overran its
+ *      step budget: every other column of that row is then 0 and its coefficients ask for no rotation),
+ *   coeffs fp64 [n][2][3] = { beta, cos beta, sin beta }.
+ *   One launch, grid (n, 2): one workgroup per (image, side), same labelling, fill and step budgets as pti_mask_compare.
+ *   workspace: pti_mask_moments_ws_bytes(n, h, w) bytes (twice pti_mask_compare's: three planes per image AND side), 4-byte
+ *   aligned; every word read is written earlier in the same launch.
+ * pti_warp_cubic: gt, pred fp32 [n][h][w] (pred is usually `cleaned`), coeffs as above (only cos and sin are read) ->
+ *   out_gt, out_pred fp32 [n][h][w] (rule 3).  One launch, grid (row tiles, n, 2), no workspace.  For coefficients that are
+ *   not a rotation the kernel still reads inside the images only.  The outputs must not alias the inputs.
+ * pti_align_bottom: rot_gt, rot_pred fp32 [n][h][w], h >= 5 -> aligned fp32 [n][h][w] (rule 4),
+ *   info int32 [n][PTI_ALIGN_BOTTOM_COLUMNS]: 0 centre_gt  1 centre_pred  2 count_gt  3 count_pred  4 shift
+ *      5 status: 0, +1 when the ground truth has no set pixel in those rows, +2 when the prediction has none; a centre
+ *      without pixels is -1, and with a non-zero status the shift is 0 (aligned is then a copy of rot_pred).
+ *   One launch, one workgroup per image, no workspace.  aligned must not alias an input.
+ * All three run on the caller's stream without a host synchronisation and are bitwise reproducible; rows do not depend on
+ * their place in the batch.  Refused before any launch: null pointers, n, h or w < 1, a threshold that is negative or NaN,
+ * a misaligned buffer, a misaligned or short workspace, aliased outputs (PTI_EINVAL); h or w above
+ * PTI_MASK_COMPARE_MAX_EDGE, n > 65535, and for pti_align_bottom h < 5 (PTI_EUNSUPPORTED).                              */
+#define PTI_MASK_MOMENTS_COLUMNS 10
+#define PTI_ALIGN_BOTTOM_COLUMNS 6
+int64_t pti_mask_moments_ws_bytes(int n, int h, int w);
+int pti_mask_moments(const float* gt, const float* pred, int n, int h, int w, float threshold, float* cleaned, int64_t* moments,
+                     double* coeffs, void* workspace, int64_t ws_bytes, pti_stream_t s);
+int pti_warp_cubic(const float* gt, const float* pred, const double* coeffs, int n, int h, int w, float* out_gt, float* out_pred,
+                   pti_stream_t s);
+int pti_align_bottom(const float* rot_gt, const float* rot_pred, int n, int h, int w, float* aligned, int32_t* info,
+                     pti_stream_t s);
 
 #ifdef __cplusplus
 }

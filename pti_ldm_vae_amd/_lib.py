@@ -60,6 +60,9 @@ MASK_COMPARE_COLUMNS = ("n_gt", "n_pred", "components_gt", "components_pred", "k
                         "intersection", "union", "gt_x", "gt_y", "gt_w", "gt_h", "pred_x", "pred_y", "pred_w", "pred_h",
                         "gt_width_upper", "gt_width_middle", "gt_width_lower",
                         "pred_width_upper", "pred_width_middle", "pred_width_lower", "status")
+# the int64 columns of pti_mask_moments' moments and the int32 columns of pti_align_bottom's info ("pair registration")
+MASK_MOMENTS_COLUMNS = ("m00", "m10", "m01", "m20", "m11", "m02", "A", "B", "C", "status")
+ALIGN_BOTTOM_COLUMNS = ("centre_gt", "centre_pred", "count_gt", "count_pred", "shift", "status")
 
 
 class DirectRepackEntry(C.Structure):
@@ -201,6 +204,10 @@ SIGNATURES = {
     "pti_full_ranks": (_I, [_P, _I64, _I, _I, _I, _P, _I64, _P]),
     "pti_coranking_fold": (_I, [_P, _I64, _P, _I64, _I, _I, _P, _P, _P]),
     "pti_shepard_fold": (_I, [_P, _I64, _P, _I64, _I, _P, _I, _P, _P, _P]),
+    "pti_mask_moments_ws_bytes": (_I64, [_I, _I, _I]),
+    "pti_mask_moments": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _I64, _P]),
+    "pti_warp_cubic": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "pti_align_bottom": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

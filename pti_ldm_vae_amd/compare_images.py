@@ -6,6 +6,7 @@ of exams within 5 / 10 pixels or above 90 / 95 / 97 %.
 
     python -m pti_ldm_vae_amd.compare_images --gt-dir edente --pred-dir edente_synth [--output-dir DIR]
     python -m pti_ldm_vae_amd.compare_images --results-dir inference_vae_<checkpoint>/results_tif
+    python -m pti_ldm_vae_amd.compare_images --results-dir ... --straighten [--write-registered DIR]
 
 ``--gt-dir`` / ``--pred-dir`` pair the ``.tif`` / ``.tiff`` files of two folders by file name (files present in one folder
 only are reported); ``--results-dir`` takes the ``[input | reconstruction]`` files ``inference_vae`` writes: the left half is
@@ -18,8 +19,17 @@ kernel's 1024-pixel edge or has no foreground on a side is skipped and listed wi
 
 Written to ``--output-dir`` (default ``<input folder>/compare``): ``_metrics.csv`` and ``_dimensions.csv`` in the reference's
 layout (``;``-separated), ``compare_metrics.json`` (per-image rows, aggregates, thresholds, skipped pairs, resolved
-arguments) and, unless ``--no-plot``, ``_metrics_distribution.png``.  Not computed: SSIM (``evaluate_vae`` reports it), the
-VGG16 feature distances, and the reference's straighten / align step."""
+arguments) and, unless ``--no-plot``, ``_metrics_distribution.png``.  Not computed: SSIM (``evaluate_vae`` reports it) and the
+VGG16 feature distances.
+
+``--straighten`` registers every pair before it is measured, as the reference does: both sides are turned until the object's
+major axis is vertical (orientation from the second moments of the filled largest component, 4 x 4 cubic rotation about
+``(w // 2, h // 2)``, replicate border), then the prediction is moved sideways until the centres of the non-zero pixels in the
+bottom fifth agree -- ``ops.register_pairs``, three more launches per batch, still one copy back.  Each image of
+``compare_metrics.json`` then carries a ``"registration"`` block (both angles in degrees, the six moments per side, both
+centres, the shift); a pair lower than 5 pixels, or with nothing in the bottom fifth of a side, is skipped with the reason.
+``--write-registered DIR`` writes ``[rotated ground truth | aligned prediction]`` per compared pair, in the layout
+``--results-dir`` reads.  Without ``--straighten`` the report is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -45,7 +55,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     parser.add_argument("--output-dir", type=Path, default=None, help="where the report goes (default: <input folder>/compare)")
     parser.add_argument("--no-plot", action="store_true", help="do not write _metrics_distribution.png")
     parser.add_argument("--seed", type=int, default=0, help="seed of the --num-samples draw (default: 0)")
+    parser.add_argument("--straighten", action="store_true",
+                        help="straighten both sides and align the prediction by the bottom fifth before measuring")
+    parser.add_argument("--write-registered", type=Path, default=None, metavar="DIR",
+                        help="with --straighten: write [rotated ground truth | aligned prediction] TIFs of the compared pairs here")
     args = parser.parse_args(argv)
+    if args.write_registered is not None and not args.straighten:
+        parser.error("--write-registered needs --straighten")
     pair_mode = args.gt_dir is not None or args.pred_dir is not None
     if pair_mode and args.results_dir is not None:
         parser.error("give either --gt-dir with --pred-dir, or --results-dir, not both")
@@ -105,15 +121,67 @@ def load_pair(gt_file: Path, pred_file: Path | None):
     return np.ascontiguousarray(gt, dtype=np.float32), np.ascontiguousarray(pred, dtype=np.float32)
 
 
-def compare_batch(gts: list, preds: list, threshold: float, device):
+NO_BOTTOM = "no foreground in the bottom 20 % of the "
+TOO_LOW = "image height {} is below 5 pixels: there is no bottom fifth to align by"
+
+
+def registration_block(moments, coeffs, align) -> dict:
+    """The ``"registration"`` entry of one image from its rows of ``ops.register_pairs``' info (host arrays: int64
+    ``[2, 10]``, float64 ``[2, 3]``, int32 ``[6]``)."""
+    from . import ops
+    a = dict(zip(ops.ALIGN_BOTTOM_COLUMNS, (int(v) for v in align)))
+    out = {}
+    for side, name in enumerate(("gt", "pred")):
+        out[f"angle_{name}_deg"] = float(np.degrees(coeffs[side][0]))
+        out[f"moments_{name}"] = dict(zip(ops.MASK_MOMENTS_COLUMNS[:6], (int(v) for v in moments[side][:6])))
+    out.update(centre_gt=a["centre_gt"], centre_pred=a["centre_pred"], shift=a["shift"])
+    return out
+
+
+def registration_skip(moments, align):
+    """The reason a registered pair is not measured, or None."""
+    from . import ops
+    from .utils import compare_metrics as M
+    status = ops.MASK_MOMENTS_COLUMNS.index("status")
+    if moments[0][status] or moments[1][status]:
+        raise RuntimeError(f"{WHO}: mask_moments reported status {int(moments[0][status])} / {int(moments[1][status])} (label loop overrun)")
+    if moments[0][0] == 0 or moments[1][0] == 0:
+        return M.NO_GT if moments[0][0] == 0 else M.NO_PRED
+    bad = int(align[ops.ALIGN_BOTTOM_COLUMNS.index("status")])
+    return NO_BOTTOM + {1: "ground truth", 2: "prediction", 3: "ground truth and the prediction"}[bad] if bad else None
+
+
+def compare_batch(gts: list, preds: list, threshold: float, device, straighten: bool = False, images: bool = False):
     """One launch and ONE copy back for a batch of one shape -> (counts int32 ``[n, 24]``, sums float64 ``[n, 3]``) on the
-    host.  Both outputs are views of one device buffer (3 doubles, then 24 int32 = 12 doubles per image)."""
+    host.  Both outputs are views of one device buffer (3 doubles, then 24 int32 = 12 doubles per image).
+
+    ``straighten``: ``ops.register_pairs`` first (three more launches, no synchronisation), the measurement is of the
+    registered pair, and a third value is returned: ``{"moments", "coeffs", "align"}`` as host arrays -- they travel in the
+    same buffer (29 more doubles per image) and the same copy; with ``images`` also ``"rotated_gt"`` and ``"aligned_pred"``."""
     import torch
 
     from . import ops
     n = len(gts)
     gt = torch.from_numpy(np.stack(gts)).to(device)
     pred = torch.from_numpy(np.stack(preds)).to(device)
+    if straighten:
+        buf = torch.empty(n * 44, dtype=torch.float64, device=device)
+        parts, at = [], 0
+        for per_image in (3, 12, 20, 6, 3):          # sums, counts, moments, coeffs, align
+            parts.append(buf[at:at + per_image * n])
+            at += per_image * n
+        sums, counts = parts[0].view(n, 3), parts[1].view(torch.int32).view(n, len(ops.MASK_COMPARE_COLUMNS))
+        moments, coeffs = parts[2].view(torch.int64).view(n, 2, 10), parts[3].view(n, 2, 3)
+        align = parts[4].view(torch.int32).view(n, len(ops.ALIGN_BOTTOM_COLUMNS))
+        rot_gt, aligned, _ = ops.register_pairs(gt, pred, threshold=threshold, out=(None, None, moments, coeffs, align))
+        ops.mask_compare(rot_gt, aligned, threshold=threshold, out=(counts, sums))
+        host = buf.cpu().numpy()
+        cut = np.cumsum([0, 3 * n, 12 * n, 20 * n, 6 * n, 3 * n])
+        reg = {"moments": host[cut[2]:cut[3]].view(np.int64).reshape(n, 2, 10).copy(), "coeffs": host[cut[3]:cut[4]].reshape(n, 2, 3).copy(),
+               "align": host[cut[4]:cut[5]].view(np.int32).reshape(n, -1).copy()}
+        if images:
+            reg["rotated_gt"], reg["aligned_pred"] = rot_gt.cpu().numpy(), aligned.cpu().numpy()
+        return host[cut[1]:cut[2]].view(np.int32).reshape(n, -1).copy(), host[:3 * n].reshape(n, 3).copy(), reg
     buf = torch.empty(n * 15, dtype=torch.float64, device=device)
     sums = buf[:3 * n].view(n, 3)
     counts = buf[3 * n:].view(torch.int32).view(n, len(ops.MASK_COMPARE_COLUMNS))
@@ -133,20 +201,35 @@ def run(args, device) -> dict:
     if args.num_samples is not None and args.num_samples < len(pairs):
         pairs = sorted(random.Random(args.seed).sample(pairs, args.num_samples))
     results, buckets = {}, {}
+    straighten = getattr(args, "straighten", False)
 
     def flush(shape):
         names, gts, preds = buckets.pop(shape)
-        counts, sums = compare_batch(gts, preds, args.threshold, device)
-        for name, row, s, m in zip(names, counts, sums, M.pair_metrics(counts, sums, *shape)):
+        reg = None
+        if straighten:
+            counts, sums, reg = compare_batch(gts, preds, args.threshold, device, True, args.write_registered is not None)
+        else:
+            counts, sums = compare_batch(gts, preds, args.threshold, device)
+        for i, (name, row, s, m) in enumerate(zip(names, counts, sums, M.pair_metrics(counts, sums, *shape))):
+            if reg is not None:
+                m = registration_skip(reg["moments"][i], reg["align"][i]) or m
             results[name] = m if isinstance(m, str) else {"metrics": m, "dimensions": M.dimensions(row),
                                                           "counts": dict(zip(ops.MASK_COMPARE_COLUMNS, (int(v) for v in row))),
                                                           "sums": dict(zip(ops.MASK_COMPARE_SUMS, (float(v) for v in s)))}
+            if reg is not None and not isinstance(m, str):
+                results[name]["registration"] = registration_block(reg["moments"][i], reg["coeffs"][i], reg["align"][i])
+                if args.write_registered is not None:
+                    from .data.tiff import write_tiff
+                    args.write_registered.mkdir(parents=True, exist_ok=True)
+                    write_tiff(str(args.write_registered / name), np.concatenate([reg["rotated_gt"][i], reg["aligned_pred"][i]], axis=1))
 
     for name, gt_file, pred_file in pairs:
         try:
             gt, pred = load_pair(gt_file, pred_file)
             if max(gt.shape) > ops.MASK_COMPARE_MAX_EDGE or min(gt.shape) < 1:
                 raise ValueError(f"image size {gt.shape} is not supported (1 .. {ops.MASK_COMPARE_MAX_EDGE} pixels per edge)")
+            if straighten and gt.shape[0] < ops.ALIGN_BOTTOM_MIN_HEIGHT:
+                raise ValueError(TOO_LOW.format(gt.shape[0]))
         except (FileNotFoundError, ValueError) as exc:
             results[name] = str(exc)
             continue
@@ -188,7 +271,7 @@ def main(argv=None) -> None:
     from .utils.cli_common import init_device_and_seed
     _lib.refuse_wrong_result_env("compare_images.py")
     args = parse_args(argv)
-    for key in ("gt_dir", "pred_dir", "results_dir", "output_dir"):
+    for key in ("gt_dir", "pred_dir", "results_dir", "output_dir", "write_registered"):
         if getattr(args, key) is not None:
             setattr(args, key, getattr(args, key).expanduser().resolve())
     if args.output_dir is None:

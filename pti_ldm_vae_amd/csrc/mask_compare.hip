@@ -361,3 +361,315 @@ extern "C" int pti_mask_compare(const float* gt, const float* pred, int n, int h
   PTI_CHECK_LAUNCH("mask_compare");
   return PTI_OK;
 }
+
+// ---- pair registration (include/pti_vae.h "pair registration"): what the reference does to a pair BEFORE it
+// measures -- straighten both sides (orientation of the object, cubic rotation), then move the prediction sideways until the
+// centres of the bottom fifth agree.  Three launches, no host synchronisation between them:
+//   mask_moments_kernel   grid (n, 2): one workgroup per (image, side) labels that side with mc_label, fills K as the
+//                         comparison kernel does, adds the six raw moments of F(K) as int64 and writes beta, cos beta, sin
+//                         beta; the prediction side also writes the cleaned prediction c
+//   warp_cubic_kernel     grid (row tiles, n, 2): 4 x 4 cubic convolution about (w / 2, h / 2), replicate border
+//   align_bottom_kernel   grid (n): centres of the bottom h / 5 rows, the shift, the shifted copy of the prediction
+namespace {
+
+constexpr int MM_COLS = PTI_MASK_MOMENTS_COLUMNS;
+constexpr int AB_COLS = PTI_ALIGN_BOTTOM_COLUMNS;
+constexpr int WC_THREADS = 256;
+constexpr int WC_ROWS = 4;     // rows of one warp_cubic workgroup
+
+struct MmArgs {
+  const float* gt;
+  const float* pred;
+  int* ws;
+  float* cleaned;       // [n][h][w]
+  long long* moments;   // [n][2][MM_COLS]
+  double* coeffs;       // [n][2][3]: beta, cos beta, sin beta
+  long long ws_ints_per_side;
+  int h, w;
+  float thr;
+};
+
+// The fill of mask_compare_kernel as a function: 4-connected union-find in B over the pixels outside the component `root` of
+// L, node 0 = outside the image.  Returns false on an overrun (block-uniform).
+__device__ bool mc_fill(int* L, int* B, int root, int h, int w, McShared& S) {
+  const int npix = h * w, tid = threadIdx.x;
+  const int budget = 2 * (npix + 3);
+  if (tid == 0) mc_st(B, 0);
+  for (int p = tid; p < npix; p += MC_THREADS) {
+    const int y = p / w, x = p - y * w;
+    const bool border = x == 0 || y == 0 || x == w - 1 || y == h - 1;
+    mc_st(B + p + 1, (border && mc_ld(L + p) != root) ? 0 : p + 1);
+  }
+  mc_phase();
+  for (int p = tid; p < npix; p += MC_THREADS) {
+    if (mc_ld(L + p) == root) continue;
+    const int y = p / w, x = p - y * w;
+    const bool N = y > 0 && mc_ld(L + p - w) != root;
+    const bool W = x > 0 && mc_ld(L + p - 1) != root;
+    const bool NW = y > 0 && x > 0 && mc_ld(L + p - w - 1) != root;
+    if (N) mc_union(B, p + 1, p - w + 1, budget, &S.err);
+    if (W && !(N && NW)) mc_union(B, p + 1, p, budget, &S.err);
+  }
+  return !mc_failed(S);
+}
+
+// Is pixel p part of F(K)?  K is the component `root` of L, B the finished fill.
+__device__ __forceinline__ bool mc_filled(int* L, int* B, int root, int p, int npix, McShared& S) {
+  if (mc_ld(L + p) == root) return true;
+  int b = 2 * (npix + 3);
+  const bool in = mc_find(B, p + 1, b) != 0;
+  if (b < 0) { S.err = 1; return false; }
+  return in;
+}
+
+__global__ __launch_bounds__(MC_THREADS) void mask_moments_kernel(MmArgs a) {
+  __shared__ McShared S;
+  __shared__ long long part[6][MC_WAVES];
+  const int img = blockIdx.x, side = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = a.h, w = a.w, npix = h * w;
+  const float* src = (side == 0 ? a.gt : a.pred) + (size_t)img * npix;
+  int* L = a.ws + ((size_t)img * 2 + side) * a.ws_ints_per_side;   // the three planes of mask_compare_kernel, per side
+  int* cnt = L + npix;
+  int* B = cnt + npix;
+  float* c = a.cleaned + (size_t)img * npix;
+  long long* mo = a.moments + ((size_t)img * 2 + side) * MM_COLS;
+  double* co = a.coeffs + ((size_t)img * 2 + side) * 3;
+
+  if (tid == 0) {
+    S.key[0] = S.key[1] = 0;
+    S.nfg[0] = S.nfg[1] = S.ncomp[0] = S.ncomp[1] = 0;
+    for (int s = 0; s < 2; ++s) {
+      S.box[s][0] = S.box[s][1] = INT_MAX;
+      S.box[s][2] = S.box[s][3] = -1;
+    }
+    S.err = 0;
+  }
+  __syncthreads();
+
+  // (With a second caller the compiler keeps mc_label<0> and mc_label<1> out of line, for mask_compare_kernel too: one call
+  // per side and workgroup, the loops are inside.  Its results are the same words; its time was measured again)
+  bool ok = side == 0 ? mc_label<0>(src, a.thr, h, w, L, cnt, S) : mc_label<1>(src, a.thr, h, w, L, cnt, S);
+  int root = MC_NONE;
+  if (ok && S.key[side]) root = (int)(0xffffffffu - (unsigned)(S.key[side] & 0xffffffffu));
+  if (ok && root != MC_NONE) ok = mc_fill(L, B, root, h, w, S);
+
+  // one pass: membership of F(K), the six sums, and on the prediction side c = pred inside P, 0 elsewhere
+  long long s0 = 0, sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0;
+  for (int p = tid; p < npix; p += MC_THREADS) {
+    const bool in = ok && root != MC_NONE && mc_filled(L, B, root, p, npix, S);
+    if (side == 1) c[p] = in ? src[p] : 0.0f;
+    if (in) {
+      const long long y = p / w, x = p - y * w;
+      s0 += 1; sx += x; sy += y; sxx += x * x; sxy += x * y; syy += y * y;
+    }
+  }
+  s0 = wave_sum(s0); sx = wave_sum(sx); sy = wave_sum(sy); sxx = wave_sum(sxx); sxy = wave_sum(sxy); syy = wave_sum(syy);
+  if (lane == 0) {
+    part[0][wave] = s0; part[1][wave] = sx; part[2][wave] = sy; part[3][wave] = sxx; part[4][wave] = sxy; part[5][wave] = syy;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  if (S.err) {   // a step budget ran out: the row says so, carries nothing else and asks for no rotation
+    for (int k = 0; k < MM_COLS; ++k) mo[k] = 0;
+    mo[MM_COLS - 1] = 1;
+    co[0] = 0.0; co[1] = 1.0; co[2] = 0.0;
+    return;
+  }
+  long long m[6];
+  for (int k = 0; k < 6; ++k) {
+    m[k] = part[k][0];
+    for (int v = 1; v < MC_WAVES; ++v) m[k] += part[k][v];
+  }
+  // m00 <= 2^20, m10 and m01 < 2^30, m20, m11 and m02 < 2^40 at 1024 x 1024: every product below is under 2^60, A, B, C and
+  // A - C fit in 61 bits and 2 B in 62 -- plain int64, exact.
+  const long long A = m[0] * m[3] - m[1] * m[1];
+  const long long Bm = m[0] * m[4] - m[1] * m[2];
+  const long long Cm = m[0] * m[5] - m[2] * m[2];
+  double beta = 0.0, cb = 1.0, sb = 0.0;
+  if (m[0] > 0) {
+    if (Bm == 0) {   // decided on the integers: an upright, mirror-symmetric or round object is not rotated at all
+      if (Cm < A) { beta = M_PI / 2; cb = 0.0; sb = 1.0; }   // the quarter turn's coefficients are exact, not cos(fp64 pi / 2)
+    } else {
+      const double theta = 0.5 * atan2((double)(2 * Bm), (double)(A - Cm));
+      beta = theta > 0.0 ? theta - M_PI / 2 : theta + M_PI / 2;
+      sincos(beta, &sb, &cb);
+    }
+  }
+  for (int k = 0; k < 6; ++k) mo[k] = m[k];
+  mo[6] = A; mo[7] = Bm; mo[8] = Cm; mo[9] = 0;
+  co[0] = beta; co[1] = cb; co[2] = sb;
+}
+
+struct WcArgs {
+  const float* src[2];
+  float* dst[2];
+  const double* coeffs;   // [n][2][3]
+  int h, w;
+};
+
+// Keys' cubic convolution weights, a = -0.75, for the taps at -1, 0, +1, +2 of a point t in [0, 1] past tap 0.  fp32, in
+// this association (the pragma keeps -ffast-math from re-associating; a multiply may still be FUSED with the add that
+// follows it -- the library is built with -ffp-contract=fast, which the pragma does not undo, and the ISA has v_fma).  At
+// t == 0 they are 0, 1, 0, 0 either way: every product and sum there is exact.
+__device__ __forceinline__ void wc_weights(float t, float* wt) {
+#pragma clang fp contract(off) reassociate(off)
+  const float a = -0.75f;
+  const float u = t + 1.0f, v = 1.0f - t;
+  wt[0] = ((a * u - 5.0f * a) * u + 8.0f * a) * u - 4.0f * a;
+  wt[1] = ((a + 2.0f) * t - (a + 3.0f)) * (t * t) + 1.0f;
+  wt[2] = ((a + 2.0f) * v - (a + 3.0f)) * (v * v) + 1.0f;
+  wt[3] = ((1.0f - wt[0]) - wt[1]) - wt[2];
+}
+
+__device__ __forceinline__ int wc_clamp(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
+
+// One workgroup: WC_ROWS output rows of one (image, side); consecutive threads take consecutive x (coalesced stores), the
+// 16 gathers go to an image that sits in L2.  Source coordinates in fp64 from the per-image coefficients, weights and sums
+// in fp32; the association of every sum is pinned and tests/mask_register_oracle.py restates it with every operation rounded
+// on its own -- the kernel's fused multiply-adds round less often, so it sits between that restatement and the fp64 oracle.
+__global__ __launch_bounds__(WC_THREADS) void warp_cubic_kernel(WcArgs a) {
+#pragma clang fp contract(off) reassociate(off)
+  const int img = blockIdx.y, side = blockIdx.z;
+  const int h = a.h, w = a.w;
+  const double* co = a.coeffs + ((size_t)img * 2 + side) * 3;
+  const double cb = co[1], sb = co[2];
+  const float* src = a.src[side] + (size_t)img * h * w;
+  float* dst = a.dst[side] + (size_t)img * h * w;
+  const int cx = w / 2, cy = h / 2;
+  const int y0 = blockIdx.x * WC_ROWS, y1 = min(y0 + WC_ROWS, h);
+  for (int y = y0; y < y1; ++y) {
+    const double dy = (double)(y - cy);
+    for (int x = threadIdx.x; x < w; x += WC_THREADS) {
+      const double dx = (double)(x - cx);
+      const double px = ((double)cx + cb * dx) - sb * dy;
+      const double py = ((double)cy + sb * dx) + cb * dy;
+      double fxd = floor(px), fyd = floor(py);
+      const float tx = (float)(px - fxd), ty = (float)(py - fyd);
+      // Further than three pixels outside, all four taps are the border pixel whatever the distance: clamping the base there
+      // changes nothing and keeps the conversion to int defined for any coefficients (NaN included: fmax / fmin drop it).
+      fxd = fmin(fmax(fxd, -3.0), (double)(w + 2));
+      fyd = fmin(fmax(fyd, -3.0), (double)(h + 2));
+      const int fx = (int)fxd, fy = (int)fyd;
+      float wx[4], wy[4];
+      wc_weights(tx, wx);
+      wc_weights(ty, wy);
+      const int x_0 = wc_clamp(fx - 1, w), x_1 = wc_clamp(fx, w), x_2 = wc_clamp(fx + 1, w), x_3 = wc_clamp(fx + 2, w);
+      float r[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float* row = src + (size_t)wc_clamp(fy - 1 + j, h) * w;
+        r[j] = ((wx[0] * row[x_0] + wx[1] * row[x_1]) + wx[2] * row[x_2]) + wx[3] * row[x_3];
+      }
+      dst[(size_t)y * w + x] = ((wy[0] * r[0] + wy[1] * r[1]) + wy[2] * r[2]) + wy[3] * r[3];
+    }
+  }
+}
+
+struct AbArgs {
+  const float* rot_gt;
+  const float* rot_pred;
+  float* aligned;
+  int* info;   // [n][AB_COLS]
+  int h, w;
+};
+
+// One workgroup per image: (count, column sum) of the non-zero pixels in the last h / 5 rows of both sides, the truncated
+// centres and their difference, then the copy of the prediction moved by that many columns with zero fill.  The sums are at
+// most 204 * 1024 * 1023 < 2^31: int32.
+__global__ __launch_bounds__(MC_THREADS) void align_bottom_kernel(AbArgs a) {
+  __shared__ int red[4][MC_WAVES];
+  __shared__ int sh_shift;
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = a.h, w = a.w, npix = h * w;
+  const float* rg = a.rot_gt + (size_t)img * npix;
+  const float* rp = a.rot_pred + (size_t)img * npix;
+  float* out = a.aligned + (size_t)img * npix;
+  int* info = a.info + (size_t)img * AB_COLS;
+  int ng = 0, sg = 0, np = 0, sp = 0;
+  for (int p = (h - h / 5) * w + tid; p < npix; p += MC_THREADS) {
+    const int x = p % w;
+    const bool g = mc_fg<0>(rg, p, 0.0f), r = mc_fg<0>(rp, p, 0.0f);
+    ng += g; sg += g ? x : 0; np += r; sp += r ? x : 0;
+  }
+  ng = wave_sum(ng); sg = wave_sum(sg); np = wave_sum(np); sp = wave_sum(sp);
+  if (lane == 0) { red[0][wave] = ng; red[1][wave] = sg; red[2][wave] = np; red[3][wave] = sp; }
+  __syncthreads();
+  if (tid == 0) {
+    int t[4];
+    for (int k = 0; k < 4; ++k) {
+      t[k] = red[k][0];
+      for (int v = 1; v < MC_WAVES; ++v) t[k] += red[k][v];
+    }
+    const int cg = t[0] ? t[1] / t[0] : -1, cp = t[2] ? t[3] / t[2] : -1;
+    const int status = (t[0] ? 0 : 1) | (t[2] ? 0 : 2);
+    const int shift = status ? 0 : cg - cp;
+    info[0] = cg; info[1] = cp; info[2] = t[0]; info[3] = t[2]; info[4] = shift; info[5] = status;
+    sh_shift = shift;
+  }
+  __syncthreads();
+  const int shift = sh_shift;
+  for (int p = tid; p < npix; p += MC_THREADS) {
+    const int x = p % w, xs = x - shift;
+    out[p] = (xs >= 0 && xs < w) ? rp[p - shift] : 0.0f;
+  }
+}
+
+inline int mr_check_shape(const char* who, int n, int h, int w) {
+  if (n < 1 || h < 1 || w < 1) PTI_FAIL(PTI_EINVAL, "%s: bad shape n=%d h=%d w=%d (all >= 1)", who, n, h, w);
+  if (h > MC_MAX_EDGE || w > MC_MAX_EDGE)
+    PTI_FAIL(PTI_EUNSUPPORTED, "%s: unsupported shape h=%d w=%d (h, w <= %d)", who, h, w, MC_MAX_EDGE);
+  if (n > 65535) PTI_FAIL(PTI_EUNSUPPORTED, "%s: unsupported batch n=%d (n <= 65535)", who, n);
+  return PTI_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t pti_mask_moments_ws_bytes(int n, int h, int w) {
+  if (n < 1 || h < 1 || w < 1 || h > MC_MAX_EDGE || w > MC_MAX_EDGE) return 0;
+  return 2 * (int64_t)n * mc_ws_ints(h, w) * (int64_t)sizeof(int);
+}
+
+extern "C" int pti_mask_moments(const float* gt, const float* pred, int n, int h, int w, float threshold, float* cleaned,
+                                int64_t* moments, double* coeffs, void* workspace, int64_t ws_bytes, pti_stream_t s) {
+  if (!gt || !pred || !cleaned || !moments || !coeffs || !workspace) PTI_FAIL(PTI_EINVAL, "mask_moments: null pointer");
+  if (const int rc = mr_check_shape("mask_moments", n, h, w)) return rc;
+  if (!(threshold >= 0.0f)) PTI_FAIL(PTI_EINVAL, "mask_moments: threshold %g must be >= 0", (double)threshold);
+  if (((uintptr_t)gt & 3) || ((uintptr_t)pred & 3) || ((uintptr_t)cleaned & 3) || ((uintptr_t)moments & 7) || ((uintptr_t)coeffs & 7))
+    PTI_FAIL(PTI_EINVAL, "mask_moments: misaligned buffer");
+  if ((uintptr_t)workspace & 3) PTI_FAIL(PTI_EINVAL, "mask_moments: workspace must be 4-byte aligned");
+  if (ws_bytes < pti_mask_moments_ws_bytes(n, h, w))
+    PTI_FAIL(PTI_EINVAL, "mask_moments: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+             (long long)pti_mask_moments_ws_bytes(n, h, w));
+  MmArgs a{gt, pred, (int*)workspace, cleaned, (long long*)moments, coeffs, mc_ws_ints(h, w), h, w, threshold};
+  PTI_LAUNCH(mask_moments_kernel, dim3((unsigned)n, 2), dim3(MC_THREADS), 0, (hipStream_t)s, a);
+  PTI_CHECK_LAUNCH("mask_moments");
+  return PTI_OK;
+}
+
+extern "C" int pti_warp_cubic(const float* gt, const float* pred, const double* coeffs, int n, int h, int w, float* out_gt,
+                              float* out_pred, pti_stream_t s) {
+  if (!gt || !pred || !coeffs || !out_gt || !out_pred) PTI_FAIL(PTI_EINVAL, "warp_cubic: null pointer");
+  if (const int rc = mr_check_shape("warp_cubic", n, h, w)) return rc;
+  if (((uintptr_t)gt & 3) || ((uintptr_t)pred & 3) || ((uintptr_t)out_gt & 3) || ((uintptr_t)out_pred & 3) || ((uintptr_t)coeffs & 7))
+    PTI_FAIL(PTI_EINVAL, "warp_cubic: misaligned buffer");
+  if (out_gt == gt || out_gt == pred || out_pred == gt || out_pred == pred || out_gt == out_pred)
+    PTI_FAIL(PTI_EINVAL, "warp_cubic: the outputs must not alias the inputs or each other");
+  WcArgs a{{gt, pred}, {out_gt, out_pred}, coeffs, h, w};
+  PTI_LAUNCH(warp_cubic_kernel, dim3((unsigned)((h + WC_ROWS - 1) / WC_ROWS), (unsigned)n, 2), dim3(WC_THREADS), 0, (hipStream_t)s, a);
+  PTI_CHECK_LAUNCH("warp_cubic");
+  return PTI_OK;
+}
+
+extern "C" int pti_align_bottom(const float* rot_gt, const float* rot_pred, int n, int h, int w, float* aligned, int32_t* info,
+                                pti_stream_t s) {
+  if (!rot_gt || !rot_pred || !aligned || !info) PTI_FAIL(PTI_EINVAL, "align_bottom: null pointer");
+  if (const int rc = mr_check_shape("align_bottom", n, h, w)) return rc;
+  if (h < 5) PTI_FAIL(PTI_EUNSUPPORTED, "align_bottom: unsupported shape h=%d (the bottom fifth needs h >= 5)", h);
+  if (((uintptr_t)rot_gt & 3) || ((uintptr_t)rot_pred & 3) || ((uintptr_t)aligned & 3) || ((uintptr_t)info & 3))
+    PTI_FAIL(PTI_EINVAL, "align_bottom: misaligned buffer");
+  if (aligned == rot_pred || aligned == rot_gt) PTI_FAIL(PTI_EINVAL, "align_bottom: the output must not alias an input");
+  AbArgs a{rot_gt, rot_pred, aligned, (int*)info, h, w};
+  PTI_LAUNCH(align_bottom_kernel, dim3((unsigned)n), dim3(MC_THREADS), 0, (hipStream_t)s, a);
+  PTI_CHECK_LAUNCH("align_bottom");
+  return PTI_OK;
+}

@@ -1280,6 +1280,128 @@ def mask_compare(gt, pred, *, threshold=0.2, out=None):
     return counts, sums
 
 
+# ---- pair registration: straighten, then align (csrc/mask_compare.hip; include/pti_vae.h "pair registration") -------------
+MASK_MOMENTS_COLUMNS = L.MASK_MOMENTS_COLUMNS              # int64 columns per (image, side)
+MASK_MOMENTS_COEFFS = ("beta", "cos_beta", "sin_beta")     # fp64 per (image, side)
+ALIGN_BOTTOM_COLUMNS = L.ALIGN_BOTTOM_COLUMNS              # int32 columns per image
+ALIGN_BOTTOM_MIN_HEIGHT = 5                                # below it there is no bottom fifth
+
+
+def _image_pair(who, names, a, b):
+    """The common checks of a pair of image batches -> (a, b, n, h, w) as ``[n, h, w]`` views."""
+    for name, t in zip(names, (a, b)):
+        if not isinstance(t, torch.Tensor) or t.dtype != F32:
+            raise TypeError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    for name, t in zip(names, (a, b)):
+        if not t.is_cuda or t.device != a.device:
+            raise ValueError(f"{who}: {name} must be a CUDA(HIP) tensor on the device of {names[0]}")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+    if a.dim() == 4 and a.shape[1] == 1:
+        a = a[:, 0]
+    if b.dim() == 4 and b.shape[1] == 1:
+        b = b[:, 0]
+    if a.dim() != 3 or b.shape != a.shape:
+        raise ValueError(f"{who}: expected [n, h, w] or [n, 1, h, w] images of one shape, got {tuple(a.shape)} / {tuple(b.shape)}")
+    n, h, w = a.shape
+    if not (1 <= n <= 65535 and 1 <= h <= MASK_COMPARE_MAX_EDGE and 1 <= w <= MASK_COMPARE_MAX_EDGE):
+        raise ValueError(f"{who}: unsupported shape {tuple(a.shape)} (1 <= n <= 65535, 1 <= h, w <= {MASK_COMPARE_MAX_EDGE})")
+    return a, b, n, h, w
+
+
+def _outs(who, out, names):
+    if out is None:
+        return (None,) * len(names)
+    if len(out) != len(names):
+        raise ValueError(f"{who}: out must be ({', '.join(names)})")
+    return tuple(out)
+
+
+def mask_moments(gt, pred, *, threshold=0.2, out=None):
+    """Orientation of the object on both sides of a batch of image pairs in one launch (``pti_mask_moments``) ->
+    ``(cleaned, moments, coeffs)`` device tensors.
+
+    ``gt`` / ``pred`` as for ``mask_compare``.  ``cleaned``: fp32 like ``pred``, the prediction inside its cleaned mask and 0
+    elsewhere.  ``moments``: int64 ``[n, 2, 10]`` in ``MASK_MOMENTS_COLUMNS`` order, side 0 the ground truth's filled largest
+    component, side 1 the prediction's; ``coeffs``: float64 ``[n, 2, 3]`` = the rotation ``beta`` (radians) that makes the
+    region's major axis vertical, its cosine and its sine (include/pti_vae.h has the rules).  A side without foreground has
+    ``m00 == 0`` and ``beta == 0``.  ``out=(cleaned, moments, coeffs)`` are written in place.  Current stream, no host sync,
+    bitwise reproducible; the scratch buffer (twice ``mask_compare``'s) is cached per (stream, shape)."""
+    who = "mask_moments"
+    gt, pred, n, h, w = _image_pair(who, ("gt", "pred"), gt, pred)
+    threshold = float(threshold)
+    if not threshold >= 0.0:
+        raise ValueError(f"{who}: threshold must be >= 0, got {threshold}")
+    out = _outs(who, out, ("cleaned", "moments", "coeffs"))
+    cleaned = _out(out[0], (n, h, w), F32, gt.device, f"{who}: out[0] (cleaned)")
+    moments = _out(out[1], (n, 2, len(MASK_MOMENTS_COLUMNS)), torch.int64, gt.device, f"{who}: out[1] (moments)")
+    coeffs = _out(out[2], (n, 2, 3), torch.float64, gt.device, f"{who}: out[2] (coeffs)")
+    nbytes = L.lib().pti_mask_moments_ws_bytes(n, h, w)
+    if nbytes <= 0:
+        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)}")
+    stream = _stream()
+    ws = _scratch("mask_moments", (n, h, w), (nbytes + 3) // 4, gt.device, stream)
+    L.check(L.lib().pti_mask_moments(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(cleaned), _ptr(moments), _ptr(coeffs),
+                                     _ptr(ws), ws.numel() * 4, stream), "pti_mask_moments")
+    return cleaned, moments, coeffs
+
+
+def warp_cubic(gt, pred, coeffs, *, out=None):
+    """Both sides of a batch rotated about ``(w // 2, h // 2)`` by their own coefficients in one launch (``pti_warp_cubic``)
+    -> ``(rotated_gt, rotated_pred)``.
+
+    ``coeffs``: float64 ``[n, 2, 3]`` as ``mask_moments`` returns them (``cos`` and ``sin`` are what is used).  4 x 4 cubic
+    convolution (Keys, a = -0.75), replicate border, fp64 coordinates, fp32 weights and sums; coefficients ``(1, 0)`` give a
+    copy.  ``out=(rotated_gt, rotated_pred)`` are written in place and must not be the inputs."""
+    who = "warp_cubic"
+    gt, pred, n, h, w = _image_pair(who, ("gt", "pred"), gt, pred)
+    if not isinstance(coeffs, torch.Tensor) or coeffs.dtype != torch.float64:
+        raise TypeError(f"{who}: coeffs must be a float64 tensor, got {getattr(coeffs, 'dtype', type(coeffs))}")
+    if coeffs.device != gt.device or not coeffs.is_contiguous() or tuple(coeffs.shape) != (n, 2, 3):
+        raise ValueError(f"{who}: coeffs must be contiguous [{n}, 2, 3] on {gt.device}, got {tuple(coeffs.shape)}")
+    out = _outs(who, out, ("rotated_gt", "rotated_pred"))
+    rot_gt = _out(out[0], (n, h, w), F32, gt.device, f"{who}: out[0] (rotated_gt)")
+    rot_pred = _out(out[1], (n, h, w), F32, gt.device, f"{who}: out[1] (rotated_pred)")
+    L.check(L.lib().pti_warp_cubic(_ptr(gt), _ptr(pred), _ptr(coeffs), n, h, w, _ptr(rot_gt), _ptr(rot_pred), _stream()),
+            "pti_warp_cubic")
+    return rot_gt, rot_pred
+
+
+def align_bottom(rot_gt, rot_pred, *, out=None):
+    """The prediction moved sideways so that the centres of the non-zero pixels in the last ``h // 5`` rows agree, in one
+    launch (``pti_align_bottom``) -> ``(aligned_pred, info)``; ``info``: int32 ``[n, 6]`` in ``ALIGN_BOTTOM_COLUMNS`` order.
+    ``status`` is 0, +1 when the ground truth has nothing in those rows, +2 when the prediction has nothing (the shift is
+    then 0).  Needs ``h >= 5``.  ``out=(aligned_pred, info)`` are written in place; ``aligned_pred`` must not be an input."""
+    who = "align_bottom"
+    rot_gt, rot_pred, n, h, w = _image_pair(who, ("rot_gt", "rot_pred"), rot_gt, rot_pred)
+    if h < ALIGN_BOTTOM_MIN_HEIGHT:
+        raise ValueError(f"{who}: unsupported shape {tuple(rot_gt.shape)} (h >= {ALIGN_BOTTOM_MIN_HEIGHT}: there is no bottom fifth)")
+    out = _outs(who, out, ("aligned_pred", "info"))
+    aligned = _out(out[0], (n, h, w), F32, rot_gt.device, f"{who}: out[0] (aligned_pred)")
+    info = _out(out[1], (n, len(ALIGN_BOTTOM_COLUMNS)), torch.int32, rot_gt.device, f"{who}: out[1] (info)")
+    L.check(L.lib().pti_align_bottom(_ptr(rot_gt), _ptr(rot_pred), n, h, w, _ptr(aligned), _ptr(info), _stream()),
+            "pti_align_bottom")
+    return aligned, info
+
+
+def register_pairs(gt, pred, *, threshold=0.2, out=None):
+    """``mask_moments``, ``warp_cubic`` and ``align_bottom`` in order: what the reference does to a pair before it measures
+    -> ``(rotated_gt, aligned_pred, info)``, ``info = {"moments", "coeffs", "align"}`` (the device tensors of the three ops).
+
+    Three launches on the current stream, no host sync.  ``out=(rotated_gt, aligned_pred, moments, coeffs, align)`` are
+    written in place; the cleaned and the rotated prediction live in scratch cached per (stream, shape)."""
+    who = "register_pairs"
+    gt, pred, n, h, w = _image_pair(who, ("gt", "pred"), gt, pred)
+    if h < ALIGN_BOTTOM_MIN_HEIGHT:
+        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)} (h >= {ALIGN_BOTTOM_MIN_HEIGHT}: there is no bottom fifth)")
+    out = _outs(who, out, ("rotated_gt", "aligned_pred", "moments", "coeffs", "align"))
+    tmp = _scratch("register_pairs", (n, h, w), 2 * n * h * w, gt.device, _stream()).view(2, n, h, w)
+    _, moments, coeffs = mask_moments(gt, pred, threshold=threshold, out=(tmp[0], out[2], out[3]))
+    rot_gt, _ = warp_cubic(gt, tmp[0], coeffs, out=(out[0], tmp[1]))
+    aligned, align = align_bottom(rot_gt, tmp[1], out=(out[1], out[4]))
+    return rot_gt, aligned, {"moments": moments, "coeffs": coeffs, "align": align}
+
+
 # ---- display normalisation (csrc/display.hip; include/pti_vae.h "display normalisation") --------------------------------
 DISPLAY_MAX_EDGE, DISPLAY_MAX_PLANES = 4096, 65535   # the bounds of pti_display_planes
 
