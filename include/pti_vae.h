@@ -48,7 +48,9 @@ typedef void* pti_stream_t; /* hipStream_t */
                                same way.
                                Still 5: pti_full_ranks / pti_coranking_fold / pti_shepard_fold appended in the same way.
                                Still 5: pti_mask_moments (+ its _ws_bytes) / pti_warp_cubic / pti_align_bottom appended in
-                               the same way. */
+                               the same way.
+                               Still 5: pti_ssim_uniform (+ its _ws_bytes) / pti_mask_compare_cleaned appended in the same
+                               way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -927,6 +929,45 @@ int pti_warp_cubic(const float* gt, const float* pred, const double* coeffs, int
                    pti_stream_t s);
 int pti_align_bottom(const float* rot_gt, const float* rot_pred, int n, int h, int w, float* aligned, int32_t* info,
                      pti_stream_t s);
+
+/* ---- uniform-window SSIM of an image pair (reference src/pti_ldm_vae/analysis/metrics.py:420:
+ *      skimage.metrics.structural_similarity(gen, gt, data_range=gt.max() - gt.min()); csrc/ssim_uniform.hip) ----
+ * x (the ground truth) and y (the cleaned prediction c of "pair registration" rule 1): fp32 [n][h][w], dense, finite,
+ * 7 <= h, w <= PTI_MASK_COMPARE_MAX_EDGE.  Per image:
+ *   W(a)(r, q) = the mean of a over rows r-3 .. r+3 and columns q-3 .. q+3, for the VALID pixels 3 <= r < h-3, 3 <= q < w-3
+ *                only.  (skimage filters the whole image with mode='reflect' and crops 3 pixels per side before it averages,
+ *                so no padded pixel ever reaches its result either.)
+ *   ux = W(x), uy = W(y), uxx = W(x x), uyy = W(y y), uxy = W(x y);      cn = 49/48 (sample covariance);
+ *   vx = cn (uxx - ux^2), vy = cn (uyy - uy^2), vxy = cn (uxy - ux uy);
+ *   R  = max(x) - min(x) over the whole image (fp32 extremes, subtracted in fp64), or data_range when it is >= 0;
+ *   C1 = (0.01 R)^2, C2 = (0.03 R)^2  (formed in fp64, rounded to fp32);
+ *   S  = ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2));   ssim = the mean of S over the (h-6)(w-6) valid pixels.
+ * Arithmetic: per pixel fp32 -- a window sum is 7 row sums (columns ascending) added rows ascending, times 1/49; products may
+ * be fused with the sum that follows them; the division is IEEE.  The moments are taken about a pixel of the window: with
+ * (a, b) = (x, y) at row 4 ((r - 3) / 4) + 5 (integer division), column q -- a pixel of the window of (r, q), the same for
+ * the four rows r that share (r - 3) / 4 -- the sums are of dx = x - a, dy = y - b, dx^2, dy^2, dx dy; ux = a + W(dx), uy = b + W(dy), and the covariances,
+ * which do not depend on the origin, are cn (W(dx^2) - W(dx)^2) and so on.  (With raw moments an object near 100 loses five
+ * digits in uxx - ux^2; with these the residuals are as small as the window's own spread.)  The mean is added in fp64 in ONE order that depends on h
+ * and w alone (thread, wave butterfly, waves in order, tiles lane-strided): no floating-point atomics, bitwise reproducible,
+ * and an image's row does not depend on n or on its place in the batch.
+ * out: fp64 [n][2] = { ssim, R }.  R == 0 (a constant x; skimage divides 0 by 0 there) gives { 0.0, 0.0 }: the caller
+ * reports "none".
+ * At most three launches on the caller's stream, no host synchronisation: per-image min / max of x (skipped when data_range
+ * >= 0), one workgroup per 32 x 32 tile of the valid region, a fixed-order finalize; R reaches the tile pass through the
+ * workspace.  No pixel outside the image is read.
+ * workspace: pti_ssim_uniform_ws_bytes(n, h, w) bytes, 8-byte aligned, ws_bytes = its size (pure host arithmetic; 0 =
+ * unsupported shape); every word read is written earlier in the same call.  Refused before any launch: null pointers, n < 1,
+ * a NaN data_range, a misaligned buffer, a misaligned or short workspace (PTI_EINVAL); h or w outside 7 ..
+ * PTI_MASK_COMPARE_MAX_EDGE, n > 65535 (PTI_EUNSUPPORTED).
+ *
+ * pti_mask_compare_cleaned is pti_mask_compare -- the same launch, the same counts and sums bit for bit -- that also writes
+ * cleaned fp32 [n][h][w] = pred inside P, 0.0f elsewhere (all 0.0f in a row whose status is 1): the y of the SSIM above and
+ * the image the MSE is formed from, without a second labelling.  cleaned must not alias gt or pred.                        */
+int64_t pti_ssim_uniform_ws_bytes(int n, int h, int w);
+int pti_ssim_uniform(const float* x, const float* y, int n, int h, int w, double data_range, double* out, void* workspace,
+                     int64_t ws_bytes, pti_stream_t s);
+int pti_mask_compare_cleaned(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts,
+                             double* sums, float* cleaned, void* workspace, int64_t ws_bytes, pti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -208,6 +208,9 @@ SIGNATURES = {
     "pti_mask_moments": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _I64, _P]),
     "pti_warp_cubic": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "pti_align_bottom": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "pti_ssim_uniform_ws_bytes": (_I64, [_I, _I, _I]),
+    "pti_ssim_uniform": (_I, [_P, _P, _I, _I, _I, _D, _P, _P, _I64, _P]),
+    "pti_mask_compare_cleaned": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _I64, _P]),
 }
 
 _lib = None

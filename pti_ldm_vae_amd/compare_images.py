@@ -7,6 +7,7 @@ of exams within 5 / 10 pixels or above 90 / 95 / 97 %.
     python -m pti_ldm_vae_amd.compare_images --gt-dir edente --pred-dir edente_synth [--output-dir DIR]
     python -m pti_ldm_vae_amd.compare_images --results-dir inference_vae_<checkpoint>/results_tif
     python -m pti_ldm_vae_amd.compare_images --results-dir ... --straighten [--write-registered DIR]
+    python -m pti_ldm_vae_amd.compare_images --results-dir ... --ssim
 
 ``--gt-dir`` / ``--pred-dir`` pair the ``.tif`` / ``.tiff`` files of two folders by file name (files present in one folder
 only are reported); ``--results-dir`` takes the ``[input | reconstruction]`` files ``inference_vae`` writes: the left half is
@@ -19,8 +20,17 @@ kernel's 1024-pixel edge or has no foreground on a side is skipped and listed wi
 
 Written to ``--output-dir`` (default ``<input folder>/compare``): ``_metrics.csv`` and ``_dimensions.csv`` in the reference's
 layout (``;``-separated), ``compare_metrics.json`` (per-image rows, aggregates, thresholds, skipped pairs, resolved
-arguments) and, unless ``--no-plot``, ``_metrics_distribution.png``.  Not computed: SSIM (``evaluate_vae`` reports it) and the
-VGG16 feature distances.
+arguments) and, unless ``--no-plot``, ``_metrics_distribution.png``.  Not computed: the VGG16 feature distances.
+
+``--ssim`` adds the reference's ``"SSIM"`` row: ``skimage.metrics.structural_similarity`` with its defaults and ``data_range =
+max(gt) - min(gt)`` -- a 7 x 7 uniform window, sample covariance, the mean with a 3-pixel border cropped off -- between the
+ground truth and the cleaned prediction (the pair the MSE is formed from; with ``--straighten`` the registered pair).  The
+``mask_compare`` launch writes the cleaned prediction, ``ops.ssim_uniform`` (csrc/ssim_uniform.hip) adds up to three launches,
+and the two doubles per image travel in the same copy back.  Each metric dictionary then carries ``"SSIM"`` right after
+``"MSE"``, ``_metrics.csv`` gains the row, and an image's ``"sums"`` block gains ``"ssim_data_range"``.  The value is ``None``
+for a constant ground truth (data range 0) and for an image with an edge below 7 pixels; such a pair keeps its other metrics
+(the reference drops it).  This is NOT ``evaluate_vae``'s SSIM (Gaussian window, zero padding, fixed range, raw reconstruction).
+Without ``--ssim`` every output is what it was.
 
 ``--straighten`` registers every pair before it is measured, as the reference does: both sides are turned until the object's
 major axis is vertical (orientation from the second moments of the filled largest component, 4 x 4 cubic rotation about
@@ -59,6 +69,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                         help="straighten both sides and align the prediction by the bottom fifth before measuring")
     parser.add_argument("--write-registered", type=Path, default=None, metavar="DIR",
                         help="with --straighten: write [rotated ground truth | aligned prediction] TIFs of the compared pairs here")
+    parser.add_argument("--ssim", action="store_true",
+                        help="also report skimage's uniform-window SSIM of the ground truth and the cleaned prediction")
     args = parser.parse_args(argv)
     if args.write_registered is not None and not args.straighten:
         parser.error("--write-registered needs --straighten")
@@ -151,21 +163,42 @@ def registration_skip(moments, align):
     return NO_BOTTOM + {1: "ground truth", 2: "prediction", 3: "ground truth and the prediction"}[bad] if bad else None
 
 
-def compare_batch(gts: list, preds: list, threshold: float, device, straighten: bool = False, images: bool = False):
+def _measure(gt, pred, threshold, counts, sums, ssim_out):
+    """``ops.mask_compare`` of a pair of device batches; with ``ssim_out`` (the ``[n, 2]`` tail of the batch's buffer) the launch
+    also writes the cleaned prediction and ``ops.ssim_uniform`` of (gt, cleaned) follows on the same stream.  A batch with an
+    edge below 7 pixels has no window: its rows are zeroed instead (range 0: ``pair_metrics`` reports ``None``)."""
+    from . import ops
+    if ssim_out is None:
+        ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums))
+    elif min(gt.shape[-2:]) < ops.SSIM_UNIFORM_MIN_EDGE:
+        ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums))
+        ssim_out.zero_()
+    else:
+        cleaned = ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums), cleaned=True)[2]
+        ops.ssim_uniform(gt, cleaned, out=ssim_out)
+
+
+def compare_batch(gts: list, preds: list, threshold: float, device, straighten: bool = False, images: bool = False,
+                  ssim: bool = False):
     """One launch and ONE copy back for a batch of one shape -> (counts int32 ``[n, 24]``, sums float64 ``[n, 3]``) on the
     host.  Both outputs are views of one device buffer (3 doubles, then 24 int32 = 12 doubles per image).
 
     ``straighten``: ``ops.register_pairs`` first (three more launches, no synchronisation), the measurement is of the
     registered pair, and a third value is returned: ``{"moments", "coeffs", "align"}`` as host arrays -- they travel in the
-    same buffer (29 more doubles per image) and the same copy; with ``images`` also ``"rotated_gt"`` and ``"aligned_pred"``."""
+    same buffer (29 more doubles per image) and the same copy; with ``images`` also ``"rotated_gt"`` and ``"aligned_pred"``.
+
+    ``ssim``: ``ops.ssim_uniform`` of the measured ground truth and the cleaned prediction after ``mask_compare`` (up to three
+    more launches), and one more value is returned LAST: float64 ``[n, 2]`` = ``{ssim, data range}`` -- two more doubles per
+    image at the end of the same buffer, the same copy."""
     import torch
 
     from . import ops
     n = len(gts)
     gt = torch.from_numpy(np.stack(gts)).to(device)
     pred = torch.from_numpy(np.stack(preds)).to(device)
+    tail = 2 * n if ssim else 0
     if straighten:
-        buf = torch.empty(n * 44, dtype=torch.float64, device=device)
+        buf = torch.empty(n * 44 + tail, dtype=torch.float64, device=device)
         parts, at = [], 0
         for per_image in (3, 12, 20, 6, 3):          # sums, counts, moments, coeffs, align
             parts.append(buf[at:at + per_image * n])
@@ -174,20 +207,22 @@ def compare_batch(gts: list, preds: list, threshold: float, device, straighten: 
         moments, coeffs = parts[2].view(torch.int64).view(n, 2, 10), parts[3].view(n, 2, 3)
         align = parts[4].view(torch.int32).view(n, len(ops.ALIGN_BOTTOM_COLUMNS))
         rot_gt, aligned, _ = ops.register_pairs(gt, pred, threshold=threshold, out=(None, None, moments, coeffs, align))
-        ops.mask_compare(rot_gt, aligned, threshold=threshold, out=(counts, sums))
+        _measure(rot_gt, aligned, threshold, counts, sums, buf[at:].view(n, 2) if ssim else None)
         host = buf.cpu().numpy()
         cut = np.cumsum([0, 3 * n, 12 * n, 20 * n, 6 * n, 3 * n])
         reg = {"moments": host[cut[2]:cut[3]].view(np.int64).reshape(n, 2, 10).copy(), "coeffs": host[cut[3]:cut[4]].reshape(n, 2, 3).copy(),
                "align": host[cut[4]:cut[5]].view(np.int32).reshape(n, -1).copy()}
         if images:
             reg["rotated_gt"], reg["aligned_pred"] = rot_gt.cpu().numpy(), aligned.cpu().numpy()
-        return host[cut[1]:cut[2]].view(np.int32).reshape(n, -1).copy(), host[:3 * n].reshape(n, 3).copy(), reg
-    buf = torch.empty(n * 15, dtype=torch.float64, device=device)
+        res = (host[cut[1]:cut[2]].view(np.int32).reshape(n, -1).copy(), host[:3 * n].reshape(n, 3).copy(), reg)
+        return res + (host[cut[5]:].reshape(n, 2).copy(),) if ssim else res
+    buf = torch.empty(n * 15 + tail, dtype=torch.float64, device=device)
     sums = buf[:3 * n].view(n, 3)
-    counts = buf[3 * n:].view(torch.int32).view(n, len(ops.MASK_COMPARE_COLUMNS))
-    ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums))
+    counts = buf[3 * n:15 * n].view(torch.int32).view(n, len(ops.MASK_COMPARE_COLUMNS))
+    _measure(gt, pred, threshold, counts, sums, buf[15 * n:].view(n, 2) if ssim else None)
     host = buf.cpu().numpy()
-    return host[3 * n:].view(np.int32).reshape(n, -1).copy(), host[:3 * n].reshape(n, 3).copy()
+    res = (host[3 * n:15 * n].view(np.int32).reshape(n, -1).copy(), host[:3 * n].reshape(n, 3).copy())
+    return res + (host[15 * n:].reshape(n, 2).copy(),) if ssim else res
 
 
 def run(args, device) -> dict:
@@ -202,20 +237,26 @@ def run(args, device) -> dict:
         pairs = sorted(random.Random(args.seed).sample(pairs, args.num_samples))
     results, buckets = {}, {}
     straighten = getattr(args, "straighten", False)
+    with_ssim = getattr(args, "ssim", False)
 
     def flush(shape):
         names, gts, preds = buckets.pop(shape)
-        reg = None
+        reg = ssim_rows = None
+        got = compare_batch(gts, preds, args.threshold, device, straighten, straighten and args.write_registered is not None, with_ssim)
+        if with_ssim:
+            got, ssim_rows = got[:-1], got[-1]
         if straighten:
-            counts, sums, reg = compare_batch(gts, preds, args.threshold, device, True, args.write_registered is not None)
+            counts, sums, reg = got
         else:
-            counts, sums = compare_batch(gts, preds, args.threshold, device)
-        for i, (name, row, s, m) in enumerate(zip(names, counts, sums, M.pair_metrics(counts, sums, *shape))):
+            counts, sums = got
+        for i, (name, row, s, m) in enumerate(zip(names, counts, sums, M.pair_metrics(counts, sums, *shape, ssim=ssim_rows))):
             if reg is not None:
                 m = registration_skip(reg["moments"][i], reg["align"][i]) or m
             results[name] = m if isinstance(m, str) else {"metrics": m, "dimensions": M.dimensions(row),
                                                           "counts": dict(zip(ops.MASK_COMPARE_COLUMNS, (int(v) for v in row))),
                                                           "sums": dict(zip(ops.MASK_COMPARE_SUMS, (float(v) for v in s)))}
+            if with_ssim and not isinstance(m, str):
+                results[name]["sums"]["ssim_data_range"] = float(ssim_rows[i][1]) if min(shape) >= ops.SSIM_UNIFORM_MIN_EDGE else None
             if reg is not None and not isinstance(m, str):
                 results[name]["registration"] = registration_block(reg["moments"][i], reg["coeffs"][i], reg["align"][i])
                 if args.write_registered is not None:
@@ -245,7 +286,8 @@ def run(args, device) -> dict:
     images = {name: results[name] for name in names if not isinstance(results[name], str)}
     skipped = [{"image": name, "reason": results[name]} for name in names if isinstance(results[name], str)]
     all_metrics = [v["metrics"] for v in images.values()]
-    return {"arguments": {k: (str(v) if isinstance(v, Path) else v) for k, v in sorted(vars(args).items())},
+    # (a run without --ssim writes the file it wrote before the flag existed: the key appears only when it is set)
+    return {"arguments": {k: (str(v) if isinstance(v, Path) else v) for k, v in sorted(vars(args).items()) if k != "ssim" or v},
             "images_processed": len(images), "images": images, "aggregates": M.aggregate(all_metrics),
             "thresholds": [{"name": n_, "count": c, "percentage": p} for n_, c, p in M.threshold_counts(all_metrics)],
             "skipped": skipped, "unpaired": unpaired}

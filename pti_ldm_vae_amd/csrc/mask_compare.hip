@@ -37,6 +37,7 @@ struct McArgs {
   int* ws;
   int* counts;      // [n][MC_COLS]
   double* sums;     // [n][3]
+  float* cleaned;   // [n][h][w] or null: pred inside P, 0 elsewhere (pti_mask_compare_cleaned)
   long long ws_ints_per_image;
   int h, w;
   float thr;
@@ -289,11 +290,14 @@ __global__ __launch_bounds__(MC_THREADS) void mask_compare_kernel(McArgs a) {
       if (G && gbox[3] > 0 && x >= gbox[0] && x < gbox[0] + gbox[2]) { gw0 += y == gr0; gw1 += y == gr1; gw2 += y == gr2; }
       if (P && x >= rbox[0] && x < rbox[0] + rbox[2]) { rw0 += y == rr0; rw1 += y == rr1; rw2 += y == rr2; }
       const float rp = P ? r : 0.0f;
+      if (a.cleaned) a.cleaned[(size_t)img * npix + p] = rp;
       const double d = (double)g - (double)rp;
       sq += d * d;
       mg = g > mg ? g : mg;
       mp = rp > mp ? rp : mp;
     }
+  } else if (a.cleaned) {   // a step budget ran out: the status column says so, the image is all background
+    for (int p = tid; p < npix; p += MC_THREADS) a.cleaned[(size_t)img * npix + p] = 0.0f;
   }
   np = wave_sum(np); inter = wave_sum(inter);
   gw0 = wave_sum(gw0); gw1 = wave_sum(gw1); gw2 = wave_sum(gw2);
@@ -343,8 +347,9 @@ extern "C" int64_t pti_mask_compare_ws_bytes(int n, int h, int w) {
   return (int64_t)n * mc_ws_ints(h, w) * (int64_t)sizeof(int);
 }
 
-extern "C" int pti_mask_compare(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts,
-                                double* sums, void* workspace, int64_t ws_bytes, pti_stream_t s) {
+namespace {
+int mc_launch(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts, double* sums,
+              float* cleaned, void* workspace, int64_t ws_bytes, pti_stream_t s) {
   if (!gt || !pred || !counts || !sums || !workspace) PTI_FAIL(PTI_EINVAL, "mask_compare: null pointer");
   if (n < 1 || h < 1 || w < 1) PTI_FAIL(PTI_EINVAL, "mask_compare: bad shape n=%d h=%d w=%d (all >= 1)", n, h, w);
   if (h > MC_MAX_EDGE || w > MC_MAX_EDGE)
@@ -356,10 +361,26 @@ extern "C" int pti_mask_compare(const float* gt, const float* pred, int n, int h
   if (ws_bytes < pti_mask_compare_ws_bytes(n, h, w))
     PTI_FAIL(PTI_EINVAL, "mask_compare: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
              (long long)pti_mask_compare_ws_bytes(n, h, w));
-  McArgs a{gt, pred, (int*)workspace, counts, sums, mc_ws_ints(h, w), h, w, threshold};
+  McArgs a{gt, pred, (int*)workspace, counts, sums, cleaned, mc_ws_ints(h, w), h, w, threshold};
   PTI_LAUNCH(mask_compare_kernel, dim3((unsigned)n), dim3(MC_THREADS), 0, (hipStream_t)s, a);
   PTI_CHECK_LAUNCH("mask_compare");
   return PTI_OK;
+}
+}  // namespace
+
+extern "C" int pti_mask_compare(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts,
+                                double* sums, void* workspace, int64_t ws_bytes, pti_stream_t s) {
+  return mc_launch(gt, pred, n, h, w, threshold, counts, sums, nullptr, workspace, ws_bytes, s);
+}
+
+// The same launch, and the same counts and sums bit for bit, with the cleaned prediction c = pred inside P, else 0 written out:
+// the second image of the pair the MSE is formed from, without a second labelling (the uniform-window SSIM reads it).
+extern "C" int pti_mask_compare_cleaned(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts,
+                                        double* sums, float* cleaned, void* workspace, int64_t ws_bytes, pti_stream_t s) {
+  if (!cleaned) PTI_FAIL(PTI_EINVAL, "mask_compare_cleaned: null pointer");
+  if ((uintptr_t)cleaned & 3) PTI_FAIL(PTI_EINVAL, "mask_compare_cleaned: misaligned buffer");
+  if (cleaned == gt || cleaned == pred) PTI_FAIL(PTI_EINVAL, "mask_compare_cleaned: the output must not alias an input");
+  return mc_launch(gt, pred, n, h, w, threshold, counts, sums, cleaned, workspace, ws_bytes, s);
 }
 
 // ---- pair registration (include/pti_vae.h "pair registration"): what the reference does to a pair BEFORE it

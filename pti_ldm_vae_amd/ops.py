@@ -1232,9 +1232,13 @@ MASK_COMPARE_COLUMNS = L.MASK_COMPARE_COLUMNS              # the int32 columns, 
 MASK_COMPARE_SUMS = ("sq_err_sum", "max_gt", "max_pred")
 
 
-def mask_compare(gt, pred, *, threshold=0.2, out=None):
+def mask_compare(gt, pred, *, threshold=0.2, out=None, cleaned=None):
     """Foreground masks, largest component, hole fill and the shape numbers of a batch of image pairs in one launch
     (``pti_mask_compare``) -> ``(counts, sums)`` device tensors.
+
+    ``cleaned``: ``None``, or ``True`` / a contiguous fp32 ``[n, h, w]`` device tensor (not ``gt`` or ``pred``): the same launch
+    (``pti_mask_compare_cleaned``) also writes the prediction inside its cleaned mask and 0 elsewhere -- the image the MSE is
+    formed from -- and ``(counts, sums, cleaned)`` is returned; ``counts`` and ``sums`` are the same bits either way.
 
     ``gt`` / ``pred``: contiguous fp32 device images ``[n, h, w]`` or ``[n, 1, h, w]`` of one shape, finite, ``1 <= h, w <=
     MASK_COMPARE_MAX_EDGE``.  Masks: ``gt != 0`` and ``|pred| > threshold``; the prediction's mask is cleaned to its largest
@@ -1275,9 +1279,65 @@ def mask_compare(gt, pred, *, threshold=0.2, out=None):
         raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)}")
     stream = _stream()
     ws = _scratch("mask_compare", (n, h, w), (nbytes + 3) // 4, gt.device, stream)
-    L.check(L.lib().pti_mask_compare(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(counts), _ptr(sums), _ptr(ws),
-                                     ws.numel() * 4, stream), "pti_mask_compare")
-    return counts, sums
+    if cleaned is None or cleaned is False:
+        L.check(L.lib().pti_mask_compare(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(counts), _ptr(sums), _ptr(ws),
+                                         ws.numel() * 4, stream), "pti_mask_compare")
+        return counts, sums
+    cleaned = _out(None if cleaned is True else cleaned, (n, h, w), F32, gt.device, f"{who}: cleaned")
+    if cleaned.data_ptr() in (gt.data_ptr(), pred.data_ptr()):
+        raise ValueError(f"{who}: cleaned must not be gt or pred")
+    L.check(L.lib().pti_mask_compare_cleaned(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(counts), _ptr(sums), _ptr(cleaned),
+                                             _ptr(ws), ws.numel() * 4, stream), "pti_mask_compare_cleaned")
+    return counts, sums, cleaned
+
+
+# ---- uniform-window SSIM of image pairs (csrc/ssim_uniform.hip; include/pti_vae.h "uniform-window SSIM") ------------------
+SSIM_UNIFORM_MIN_EDGE = 7                               # the 7 x 7 window must fit
+SSIM_UNIFORM_COLUMNS = ("ssim", "data_range")
+
+
+def ssim_uniform(gt, pred, *, data_range=None, out=None):
+    """skimage's uniform-window SSIM of a batch of image pairs (``pti_ssim_uniform``) -> fp64 ``[n, 2]`` device tensor in
+    ``SSIM_UNIFORM_COLUMNS`` order.
+
+    ``gt`` / ``pred``: contiguous fp32 device images ``[n, h, w]`` or ``[n, 1, h, w]`` of one shape, finite, ``7 <= h, w <=
+    MASK_COMPARE_MAX_EDGE``; ``pred`` is usually ``mask_compare``'s ``cleaned``.  7 x 7 box window, sample covariance, the mean
+    over the pixels whose window lies inside the image (a 3-pixel border is left out), ``K1, K2 = 0.01, 0.03``.
+    ``data_range``: ``None`` takes ``max(gt) - min(gt)`` per image on the device, a number ``>= 0`` is used for every image.
+    An image whose range is 0 reports ``{0, 0}`` (the SSIM is 0 / 0 there).  ``out`` is written in place.  At most three
+    launches on the current stream, no host sync; bitwise reproducible; the scratch buffer is cached per (stream, shape)."""
+    who = "ssim_uniform"
+    for name, t in (("gt", gt), ("pred", pred)):
+        if not isinstance(t, torch.Tensor) or t.dtype != F32:
+            raise TypeError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if data_range is not None:
+        data_range = float(data_range)
+        if not data_range >= 0.0:
+            raise ValueError(f"{who}: data_range must be >= 0 or None, got {data_range}")
+    for name, t in (("gt", gt), ("pred", pred)):
+        if not t.is_cuda or t.device != gt.device:
+            raise ValueError(f"{who}: {name} must be a CUDA(HIP) tensor on the device of gt")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+    if gt.dim() == 4 and gt.shape[1] == 1:
+        gt = gt[:, 0]
+    if pred.dim() == 4 and pred.shape[1] == 1:
+        pred = pred[:, 0]
+    if gt.dim() != 3 or pred.shape != gt.shape:
+        raise ValueError(f"{who}: expected [n, h, w] or [n, 1, h, w] images of one shape, got {tuple(gt.shape)} / {tuple(pred.shape)}")
+    n, h, w = gt.shape
+    lo, hi = SSIM_UNIFORM_MIN_EDGE, MASK_COMPARE_MAX_EDGE
+    if not (1 <= n <= 65535 and lo <= h <= hi and lo <= w <= hi):
+        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)} (1 <= n <= 65535, {lo} <= h, w <= {hi})")
+    out = _out(out, (n, len(SSIM_UNIFORM_COLUMNS)), torch.float64, gt.device, f"{who}: out")
+    nbytes = L.lib().pti_ssim_uniform_ws_bytes(n, h, w)
+    if nbytes <= 0:
+        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)}")
+    stream = _stream()
+    ws = _scratch("ssim_uniform", (n, h, w), (nbytes + 3) // 4, gt.device, stream)
+    L.check(L.lib().pti_ssim_uniform(_ptr(gt), _ptr(pred), n, h, w, -1.0 if data_range is None else data_range, _ptr(out),
+                                     _ptr(ws), ws.numel() * 4, stream), "pti_ssim_uniform")
+    return out
 
 
 # ---- pair registration: straighten, then align (csrc/mask_compare.hip; include/pti_vae.h "pair registration") -------------

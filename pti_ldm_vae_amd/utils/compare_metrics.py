@@ -2,8 +2,11 @@
 from the integer table and the three fp64 sums of ``ops.mask_compare`` to the per-pair metrics, their aggregates with the
 reference's five outlier counts, the twelve threshold counts and the rows of its two CSV files.  No torch, fp64 throughout.
 
-What is not here: SSIM, the VGG16 cosine similarity and Euclidean distance, and the straighten / align step that the
-reference runs before measuring."""
+``pair_metrics(..., ssim=...)`` adds the reference's ``"SSIM"`` row from ``ops.ssim_uniform``'s two numbers per pair (skimage's
+uniform-window SSIM of the ground truth and the cleaned prediction); without the argument nothing changes.
+
+What is not here: the VGG16 cosine similarity and Euclidean distance; the straighten / align step that the
+reference runs before measuring happens on the device before these numbers are taken."""
 from __future__ import annotations
 
 import math
@@ -18,6 +21,10 @@ METRIC_KEYS = ("MSE", "PSNR", "Dice Coefficient", "Dice Loss", "IoU", "Height Me
 # higher is better (metrics.py:465-475); for every other key the worst value is the largest
 HIGHER_IS_BETTER = frozenset(("PSNR", "Dice Coefficient", "Height Metric", "Width Metric Upper", "Width Metric Middle",
                               "Width Metric Lower", "IoU"))
+# the optional row of ``pair_metrics(..., ssim=...)`` is higher-is-better too; kept apart so that the set above stays the
+# flagless report's
+HIGHER_IS_BETTER_OPTIONAL = frozenset(("SSIM",))
+SSIM_MIN_EDGE = 7   # the uniform window of ``ops.ssim_uniform``: a smaller image has no SSIM
 OUTLIER_KEYS = ("outside_1_ci", "outside_2_ci", "outside_3_ci", "outside_iqr", "outside_z")
 DIMENSION_COLUMNS = ("Image Path", "GT Height", "GT Width Upper", "GT Width Middle", "GT Width Lower", "Gen Height",
                      "Gen Width Upper", "Gen Width Middle", "Gen Width Lower")
@@ -43,9 +50,13 @@ def dimensions(row) -> dict:
             "Gen Width Middle": c["pred_width_middle"], "Gen Width Lower": c["pred_width_lower"]}
 
 
-def pair_metrics(counts, sums, h: int, w: int) -> list:
+def pair_metrics(counts, sums, h: int, w: int, ssim=None) -> list:
     """Per image either the metric dictionary (``METRIC_KEYS`` in order) or, for a pair that is skipped, the reason as a
     string: a side without any foreground component has no box to measure (the reference's ``except`` drops such a pair).
+
+    ``ssim``: float64 ``[n, 2]`` = ``{ssim, data range}`` as ``ops.ssim_uniform`` returns them (host array); every dictionary
+    then carries ``"SSIM"`` right after ``"MSE"`` (the reference's order).  It is ``None`` when the data range is 0 (a constant
+    ground truth: 0 / 0) or when an edge is below ``SSIM_MIN_EDGE`` (no 7 x 7 window fits); such a pair keeps its other metrics.
 
     ``counts`` int ``[n, 24]`` / ``sums`` float64 ``[n, 3]`` as ``ops.mask_compare`` returns them (host arrays), ``h, w`` the
     image size.  PSNR is ``inf`` at MSE 0 and ``None`` when neither image has a positive pixel; a ratio is ``None`` when
@@ -57,6 +68,10 @@ def pair_metrics(counts, sums, h: int, w: int) -> list:
     npix = int(h) * int(w)
     if npix < 1:
         raise ValueError(f"pair_metrics: bad image size {h} x {w}")
+    if ssim is not None:
+        ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 2)
+        if len(ssim) != len(counts):
+            raise ValueError(f"pair_metrics: {len(counts)} count rows but {len(ssim)} ssim rows")
     out = []
     for i, (row, (sq, max_gt, max_pred)) in enumerate(zip(counts, sums)):
         c = dict(zip(COLUMNS, (int(v) for v in row)))
@@ -81,6 +96,9 @@ def pair_metrics(counts, sums, h: int, w: int) -> list:
              "Absolute Width Middle Difference": abs(d["GT Width Middle"] - d["Gen Width Middle"]),
              "Absolute Width Lower Difference": abs(d["GT Width Lower"] - d["Gen Width Lower"])}
         assert tuple(m) == METRIC_KEYS
+        if ssim is not None:
+            value = None if (ssim[i][1] == 0 or min(int(h), int(w)) < SSIM_MIN_EDGE) else float(ssim[i][0])
+            m = {"MSE": m.pop("MSE"), "SSIM": value, **m}
         out.append(m)
     return out
 
@@ -116,7 +134,7 @@ def aggregate(all_metrics: list) -> dict:
                 "outside_iqr": int(np.sum((data < q1 - 1.5 * iqr) | (data > q3 + 1.5 * iqr))),
                 "outside_z": 0 if std == 0 else int(np.sum(np.abs((data - mean) / std) > 3)),
             }
-        worst = float(data.min() if key in HIGHER_IS_BETTER else data.max())
+        worst = float(data.min() if key in HIGHER_IS_BETTER or key in HIGHER_IS_BETTER_OPTIONAL else data.max())
         out[key] = {"n": n, "none": none, "mean": mean, "std": std, "ci95": [lo, hi], "worst": worst, "outliers": outliers}
     return out
 
