@@ -179,7 +179,9 @@ int pti_direct_repack(const pti_direct_repack_table* t, pti_stream_t s);
  * for every narrow channel k < cn; wide is dense NHWC bf16 with cw channels (prologue P optional),
  * narrow is fp32/bf16 with element strides narrow_stride[n,h,w,c].  dbias_wide[cw] += column sums
  * of wide, dbias_narrow[k] += sum of narrow (either may be NULL).  Per-block partials go to `workspace`
- * (plain stores) and are summed in block order by a second launch: deterministic, += into the outputs.  */
+ * (plain stores) and are summed in block order by a second launch: deterministic, += into the outputs.
+ * The per-block partial size is cn * (80 * (cw / 8) + 1) floats.  The launch halves its block count until its partials
+ * fit workspace_bytes; a workspace smaller than one block's partials is refused (PTI_EINVAL) before any launch.  */
 int pti_wgrad_direct(const void* wide, const void* narrow, float* dw, float* dbias_wide,
                      float* dbias_narrow, const int64_t* in_stats, const float* gamma,
                      const float* beta, int n, int h, int w, int cw, int cn, int ksize, int sgn,
