@@ -3,9 +3,8 @@
 // per-row sums.  4 <= n <= 8192.  DESIGN.md 5s.
 //
 //   pti_full_ranks, one launch: one workgroup per row, 256 threads up to 2048 columns and 1024 above (measured: DESIGN.md
-//     5s).  The row becomes pti_umap_knn's 64-bit keys in LDS (the fp32 bits, -0 stored as 0, above the column), padded
-//     to a power of two with all-ones keys (64 KB at n = 8192).  A
-//     bitonic network sorts the whole row; no two keys are equal, so any correct sort gives the same result.  Every thread
+//     5s).  The row becomes pti_umap_knn's 64-bit keys in LDS (neighbor_order_key, pti_common.h), padded to a power of two
+//     with all-ones keys (64 KB at n = 8192).  A bitonic network sorts the whole row; no two keys are equal, so any correct sort gives the same result.  Every thread
 //     then takes the columns at its positions into registers (at most 8), the thread that meets the row's own column
 //     publishes its position, and after a barrier the positions are scattered into an int16 row that REUSES the keys'
 //     LDS: rank = position + 1, less one past the own column's position, 0 at the own column.  The row leaves with 16-byte
@@ -52,11 +51,7 @@ __global__ __launch_bounds__(CR_SORT_THREADS) void full_ranks_kernel(const float
   const float* __restrict__ row = dist + (long long)r * ldd;
   for (int j = tid; j < np2; j += CR_SORT_THREADS) {
     cr_key v = ~0ull;                                      // padding sorts last
-    if (j < n) {
-      uint32_t bits = __float_as_uint(row[j]);
-      if (bits == 0x80000000u) bits = 0;                   // -0 is 0
-      v = ((cr_key)bits << 32) | (uint32_t)j;
-    }
+    if (j < n) v = neighbor_order_key(row[j], j);
     cr_keys[j] = v;
   }
   __syncthreads();

@@ -2,8 +2,8 @@
 // projection-quality report of the latent-space analysis (trustworthiness, continuity, neighbourhood preservation, kNN label
 // agreement, silhouette).  3 <= n <= 8192.  DESIGN.md 5r.
 //
-//   pti_neighbor_ranks, one launch: one 256-thread workgroup per row i.  The row's fp32 words (-0 stored as 0) are staged once
-//     in LDS, padded to a multiple of four with all-ones words (32 KB at n = 8192, so four workgroups share a compute unit).
+//   pti_neighbor_ranks, one launch: one 256-thread workgroup per row i.  The row's fp32 words (neighbor_order_bits, pti_common.h) are staged
+//     once in LDS, padded to a multiple of four with all-ones words (32 KB at n = 8192, so four workgroups share a compute unit).
 //     The four waves take the m listed neighbours round-robin; for neighbour j a lane reads four consecutive words per step
 //     (one 16-byte LDS read, lane-contiguous: conflict-free) and counts the columns l with key(i, l) < key(i, j), where key is
 //     pti_umap_knn's 64-bit key, the word above the column: word_l < word_j, or equal words and l < j.  A padding word is all
@@ -43,10 +43,7 @@ __global__ __launch_bounds__(PQ_THREADS) void neighbor_ranks_kernel(const float*
   const float* __restrict__ row = dist + (long long)i * ldd;
   for (int l = tid; l < np4; l += PQ_THREADS) {
     uint32_t bits = 0xffffffffu;                         // padding: never below a key of a real column
-    if (l < n) {
-      bits = __float_as_uint(row[l]);
-      if (bits == 0x80000000u) bits = 0;                 // -0 is 0
-    }
+    if (l < n) bits = neighbor_order_bits(row[l]);
     pq_word[l] = bits;
   }
   __syncthreads();

@@ -211,12 +211,26 @@ __device__ __forceinline__ f32x2 gn_silu2(f32x2 x, f32x2 sc, f32x2 sh) {
 }
 
 // lowbias32 (Chris Wellons, "Prospecting for hash functions", public domain): a 32-bit bijection with good avalanche;
-// the counter-based generator of the augmentation noise and of UMAP's negative samples
-__device__ __forceinline__ uint32_t lowbias32(uint32_t h) {
+// the counter-based generator of the augmentation noise and of UMAP's negative samples (pti_umap_epoch hashes the
+// epoch's base on the host)
+__host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t h) {
   h ^= h >> 16; h *= 0x7feb352du;
   h ^= h >> 15; h *= 0x846ca68bu;
   h ^= h >> 16;
   return h;
+}
+
+// The neighbour order: the columns of a row of non-negative fp32 distances go by (distance, then column; -0 is 0).
+// The bits of a non-negative float order as the float does, so with the column below them one 64-bit integer compare
+// decides, and no two keys of a row are equal.  pti_umap_knn / pti_umap_knn_cross select by it, pti_neighbor_ranks and
+// pti_full_ranks rank by it; all-ones (bits or key) is their padding, above every real entry.
+__device__ __forceinline__ uint32_t neighbor_order_bits(float d) {
+  uint32_t bits = __float_as_uint(d);
+  if (bits == 0x80000000u) bits = 0;   // -0 is 0
+  return bits;
+}
+__device__ __forceinline__ unsigned long long neighbor_order_key(float d, int column) {
+  return ((unsigned long long)neighbor_order_bits(d) << 32) | (uint32_t)column;
 }
 
 // ---- wave and workgroup reductions ----------------------------------------------------------------------

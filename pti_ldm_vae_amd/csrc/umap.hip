@@ -3,9 +3,8 @@
 // and one layout epoch in buffered (Jacobi) form.  3 <= N <= 8192, 2 <= k <= 256, k < N, two output columns, at most 2000
 // epochs.  DESIGN.md 5l.
 //
-//   pti_umap_knn, one launch: one 256-thread workgroup per row.  Every entry becomes one 64-bit key in LDS -- the bits of
-//     the non-negative fp32 distance above the column -- so that integer order is the order (distance, column) and no two
-//     keys are equal.  With m = the power of two >= k: a bitonic network sorts every run of m keys (alternating
+//   pti_umap_knn, one launch: one 256-thread workgroup per row.  Every entry becomes one 64-bit key in LDS
+//     (neighbor_order_key, pti_common.h: integer order is the order (distance, column) and no two keys are equal).  With m = the power of two >= k: a bitonic network sorts every run of m keys (alternating
 //     directions), then log2(N / m) rounds keep the m smallest of two neighbouring runs (element-wise minimum of an
 //     ascending and a descending run: a bitonic run that holds them) and merge that run again.  Each round halves the
 //     data, so the cost is that of sorting runs of m, not of sorting the row.  Comparisons only: exact.
@@ -81,11 +80,7 @@ __global__ __launch_bounds__(UM_THREADS) void umap_knn_kernel(const float* __res
   const int i = blockIdx.x, tid = threadIdx.x, m = 1 << lm;
   for (int j = tid; j < np2; j += UM_THREADS) {
     um_key v = ~0ull;                                    // padding sorts last
-    if (j < n) {
-      uint32_t bits = __float_as_uint(dist[(long long)i * ldd + j]);
-      if (bits == 0x80000000u) bits = 0;                 // -0 is 0
-      v = ((um_key)bits << 32) | (uint32_t)j;
-    }
+    if (j < n) v = neighbor_order_key(dist[(long long)i * ldd + j], j);
     key[j] = v;
   }
   __syncthreads();
@@ -659,11 +654,7 @@ extern "C" int pti_umap_epoch(const int* indptr, const int* indices, const int* 
   u.n = n;
   u.epoch = epoch;
   u.negatives = negative_sample_rate;
-  uint32_t h = seed + (uint32_t)epoch;                   // lowbias32 on the host: the same three lines as on the device
-  h ^= h >> 16; h *= 0x7feb352du;
-  h ^= h >> 15; h *= 0x846ca68bu;
-  h ^= h >> 16;
-  u.base = h;
+  u.base = lowbias32(seed + (uint32_t)epoch);
   PTI_LAUNCH(umap_epoch_kernel, dim3(cdiv(n, UM_THREADS / 64)), dim3(UM_THREADS), 0, (hipStream_t)s, u);
   PTI_CHECK_LAUNCH("umap_epoch");
   return PTI_OK;

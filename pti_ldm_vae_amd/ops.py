@@ -20,6 +20,8 @@ BF16 = torch.bfloat16
 F16 = torch.float16
 F32 = torch.float32
 I64 = torch.int64
+I32 = torch.int32
+I16 = torch.int16
 STAT_SCALE = 65536.0   # GroupNorm statistics are Q47.16 fixed-point int64 {sum, sum of squares} (pti_common.h)
 ACT16 = (BF16, F16)   # storage formats of a forward activation (flag derived from the tensor's dtype)
 LATENT_BWD_MAX_BLOCKS = 512   # PTI_LATENT_BWD_MAX_BLOCKS / PTI_VAE_LOSS_MAX_BLOCKS / PTI_POST_QUANT_BWD_MAX_BLOCKS of
@@ -756,7 +758,95 @@ def preprocess_batch(src, offsets, hw, out, stats=None):
     return out
 
 
-# ---- evaluation metrics (csrc/image_metrics.hip; include/pti_vae.h "evaluation metrics") ------------------------------
+# ---- argument checks shared by the analysis and evaluation launchers below ------------------------------------------------
+# Their callers hand in arrays, None and views of larger buffers, so these say more than _chk / _out / _scratch; the
+# training launchers above never come through here.
+def _tensor(t, dtype, name, dims=None):
+    """_chk for an argument that may not be a tensor at all."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
+    _chk(t, dtype, name, dims)
+
+
+def _dense_rows(t, name, dtype=F32, *, square=False, copy=False):
+    """-> ``t`` as a device matrix of ``dtype`` whose rows are dense (column stride 1, row stride >= columns), a
+    row-strided slice included.  It is used in place and anything else is refused (a copy would hide the caller's
+    buffer), unless ``copy``: then any non-empty floating-point matrix is taken and cast / copied once where it has to be."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
+    if copy and not t.is_floating_point():
+        raise TypeError(f"{name}: expected a floating-point matrix, got {t.dtype}")
+    if not copy and t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    want = (f"{name}: expected {'a square [n, n]' if square else 'an [m, n]'} matrix {'that is not empty' if copy else 'with dense rows'}, "
+            f"got {tuple(t.shape)}")
+    if t.dim() != 2 or (square and t.shape[0] != t.shape[1]) or (copy and 0 in t.shape):
+        raise ValueError(want)
+    if copy and t.dtype != dtype:
+        t = t.to(dtype)
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        if not copy:
+            raise ValueError(want)
+        t = t.contiguous()
+    return t
+
+
+def _rows_out(out, shape, dtype, device, name):
+    """Not _out: a view with a row stride is written in place, so the rule is dense rows, not contiguity."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _dense_rows(out, f"{name}: out", dtype)
+    if tuple(out.shape) != tuple(shape) or out.device != device:
+        raise ValueError(f"{name}: out must be {list(shape)} on {device}")
+    return out
+
+
+def _outs(who, out, names):
+    """The tuple of caller-owned outputs ``out=(a, b, ...)``, or as many ``None``."""
+    if out is None:
+        return (None,) * len(names)
+    if len(out) != len(names):
+        raise ValueError(f"{who}: out must be ({', '.join(names)})")
+    return tuple(out)
+
+
+def _scratch_bytes(who, kind, shape, nbytes, what, device, stream):
+    """_scratch for a launcher whose workspace the library sizes in bytes (``nbytes`` from its ``pti_*_ws_bytes``; none
+    for a shape it does not serve) -> (buffer, its size in bytes)."""
+    if nbytes <= 0:
+        raise ValueError(f"{who}: unsupported shape {what}")
+    ws = _scratch(kind, shape, (nbytes + 3) // 4, device, stream)
+    return ws, ws.numel() * 4
+
+
+def _offsets(who, name, seg, device, what, host=False):
+    """An int32 vector of ``what`` + 1 row offsets on ``device`` (``host``: or in host memory)."""
+    if not isinstance(seg, torch.Tensor) or (seg.device != device and (seg.is_cuda or not host)):
+        raise ValueError(f"{who}: {name} must be a CUDA(HIP) tensor on {device}")
+    if seg.dtype != I32:
+        raise TypeError(f"{who}: {name} must be int32, got {seg.dtype}")
+    if seg.dim() != 1 or seg.numel() < 2 or not seg.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous vector of {what} + 1 offsets")
+
+
+def _latent_attrs(who, z, attrs):
+    """The latent table ``z`` [N, L] in any layout and the attribute table ``attrs`` [na, N] -> (zt, attrs, n, l, na, ldz,
+    lda): both as fp32 with dense rows of ``n`` values, ``zt`` = ``z`` transposed (the kernels read channel-major rows)
+    -- a transposed view of a channel-major buffer is used in place, anything else is copied once -- and their row
+    strides."""
+    for name, t in (("z", z), ("attrs", attrs)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
+        if not t.is_floating_point():
+            raise TypeError(f"{who}: {name}: expected a floating-point matrix, got {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"{who}: {name}: expected a matrix, got {tuple(t.shape)}")
+    n, l = z.shape
+    na = attrs.shape[0]
+    if attrs.shape[1] != n or attrs.device != z.device:
+        raise ValueError(f"{who}: z {tuple(z.shape)} needs attrs [na, {n}] on {z.device}, got {tuple(attrs.shape)} on {attrs.device}")
+    zt, attrs = _dense_rows(z.t(), f"{who}: z", copy=True), _dense_rows(attrs, f"{who}: attrs", copy=True)
+    return zt, attrs, n, l, na, (zt.stride(0) if l > 1 else n), (attrs.stride(0) if na > 1 else n)   # a single row's stride means nothing
 SSIM_WINDOW, SSIM_SIGMA = 11, 1.5
 _ssim_taps = None
 
@@ -803,35 +893,6 @@ def image_metrics(pred, target, *, clamp=None, data_range=1.0, k1=0.01, k2=0.03,
 
 
 # ---- latent-space analysis (csrc/latent_stats.hip; include/pti_vae.h "latent-space analysis") -------------------------
-def _rows(t, name):
-    """-> ``t`` as an fp32 device matrix whose rows are dense (column stride 1, row stride >= columns); a view that
-    already is one (a row-strided slice included) is passed through without a copy."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
-    if not t.is_floating_point():
-        raise TypeError(f"{name}: expected a floating-point matrix, got {t.dtype}")
-    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{name}: expected a non-empty [n, d] matrix, got {tuple(t.shape)}")
-    if t.dtype != F32:
-        t = t.to(F32)
-    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        t = t.contiguous()
-    return t
-
-
-def _latent_out(out, shape, like, name):
-    """Not _out: a view with a row stride is written in place, so the rule is dense rows, not contiguity."""
-    if out is None:
-        return torch.empty(shape, dtype=F32, device=like.device)
-    if not isinstance(out, torch.Tensor) or not out.is_cuda:
-        raise ValueError(f"{name}: out must be a CUDA(HIP) tensor")
-    if out.dtype != F32:
-        raise TypeError(f"{name}: out must be fp32, got {out.dtype}")
-    if tuple(out.shape) != tuple(shape) or out.device != like.device or out.stride(1) != 1 or out.stride(0) < shape[1]:
-        raise ValueError(f"{name}: out must be {list(shape)} on {like.device} with dense rows")
-    return out
-
-
 def latent_pairwise(a, b=None, *, mode="dist", center=None, out=None):
     """``out[i, j]`` = Euclidean distance (``mode="dist"``) or dot product (``mode="dot"``) of row ``i`` of ``a`` [n1, d]
     and row ``j`` of ``b`` [n2, d] (``b=None``: ``a`` against itself) -> fp32 ``[n1, n2]`` device tensor
@@ -841,8 +902,8 @@ def latent_pairwise(a, b=None, *, mode="dist", center=None, out=None):
     are used in place.  Runs on the current stream, no host sync; the scratch buffer is cached per (stream, shape)."""
     if mode not in ("dist", "dot"):
         raise ValueError(f"latent_pairwise: mode must be 'dist' or 'dot', got {mode!r}")
-    a = _rows(a, "latent_pairwise: a")
-    b = a if b is None else _rows(b, "latent_pairwise: b")
+    a = _dense_rows(a, "latent_pairwise: a", copy=True)
+    b = a if b is None else _dense_rows(b, "latent_pairwise: b", copy=True)
     if b.shape[1] != a.shape[1] or b.device != a.device:
         raise ValueError(f"latent_pairwise: a {tuple(a.shape)} and b {tuple(b.shape)} must share columns and device")
     n1, d = a.shape
@@ -858,7 +919,7 @@ def latent_pairwise(a, b=None, *, mode="dist", center=None, out=None):
     floats = L.lib().pti_latent_pairwise_ws_floats(n1, n2, d)
     if floats <= 0:
         raise ValueError(f"latent_pairwise: unsupported shape a {tuple(a.shape)} b {tuple(b.shape)}")
-    out = _latent_out(out, (n1, n2), a, "latent_pairwise")
+    out = _rows_out(out, (n1, n2), F32, a.device, "latent_pairwise")
     stream = _stream()
     ws = _scratch("pair", (n1, n2, d), floats, a.device, stream)
     L.check(L.lib().pti_latent_pairwise(_ptr(a), a.stride(0), n1, _ptr(b), b.stride(0), n2, d, _ptr(center),
@@ -872,17 +933,12 @@ def latent_group_stats(a, seg_a, b, seg_b, *, out=None):
     ``compute_distance_metrics`` for every patient at once.  ``a`` [n1, d] / ``b`` [n2, d] hold each patient's rows
     consecutively; ``seg_a`` / ``seg_b`` are int32 device vectors of ``patients + 1`` ascending row offsets.  A patient
     without rows on one side gets a NaN row.  Runs on the current stream, no host sync."""
-    a = _rows(a, "latent_group_stats: a")
-    b = _rows(b, "latent_group_stats: b")
+    a = _dense_rows(a, "latent_group_stats: a", copy=True)
+    b = _dense_rows(b, "latent_group_stats: b", copy=True)
     if b.shape[1] != a.shape[1] or b.device != a.device:
         raise ValueError(f"latent_group_stats: a {tuple(a.shape)} and b {tuple(b.shape)} must share columns and device")
-    for name, seg in (("seg_a", seg_a), ("seg_b", seg_b)):
-        if not isinstance(seg, torch.Tensor) or not seg.is_cuda or seg.device != a.device:
-            raise ValueError(f"latent_group_stats: {name} must be a CUDA(HIP) tensor on {a.device}")
-        if seg.dtype != torch.int32:
-            raise TypeError(f"latent_group_stats: {name} must be int32, got {seg.dtype}")
-        if seg.dim() != 1 or seg.numel() < 2 or not seg.is_contiguous():
-            raise ValueError(f"latent_group_stats: {name} must be a contiguous vector of patients + 1 offsets")
+    _offsets("latent_group_stats", "seg_a", seg_a, a.device, "patients")
+    _offsets("latent_group_stats", "seg_b", seg_b, a.device, "patients")
     if seg_a.numel() != seg_b.numel():
         raise ValueError("latent_group_stats: seg_a and seg_b must describe the same patients")
     e = seg_a.numel() - 1
@@ -890,7 +946,7 @@ def latent_group_stats(a, seg_a, b, seg_b, *, out=None):
     floats = L.lib().pti_latent_group_stats_ws_floats(n1, n2, e, d)
     if floats <= 0:
         raise ValueError(f"latent_group_stats: unsupported shape a {tuple(a.shape)} b {tuple(b.shape)} patients {e}")
-    out = _latent_out(out, (e, 4), a, "latent_group_stats")
+    out = _rows_out(out, (e, 4), F32, a.device, "latent_group_stats")
     if out.stride(0) != 4:
         raise ValueError("latent_group_stats: out must be contiguous")
     stream = _stream()
@@ -901,24 +957,13 @@ def latent_group_stats(a, seg_a, b, seg_b, *, out=None):
 
 
 # ---- exact t-SNE (csrc/tsne.hip; include/pti_vae.h "exact t-SNE") -------------------------------------------------------
-def _tsne_matrix(t, name):
-    """An fp32 device matrix [n, n] with dense rows, used in place (never copied: a copy would hide the caller's buffer)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
-    if t.dtype != F32:
-        raise TypeError(f"{name}: expected fp32, got {t.dtype}")
-    if t.dim() != 2 or t.shape[0] != t.shape[1] or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        raise ValueError(f"{name}: expected a square [n, n] matrix with dense rows, got {tuple(t.shape)}")
-    return t
-
-
 def tsne_affinities(d2, perplexity, *, out=None):
     """Joint probabilities of exact t-SNE (``pti_tsne_affinities``) from the fp32 matrix ``d2`` [n, n] of SQUARED Euclidean
     distances -> ``(P, sums)``: ``P`` fp32 [n, n], symmetric bit for bit with a zero diagonal (sklearn's
     ``_joint_probabilities`` in dense form: the per-row perplexity search in fp64, then ``max((p_j|i + p_i|j) / S, eps)``),
     and ``sums`` = the fp64 device pair ``{sum P log P, sum P}`` that ``tsne_step`` needs for the KL value.
     2 <= n <= 8192, 0 < perplexity < n.  Runs on the current stream, no host sync."""
-    d2 = _tsne_matrix(d2, "tsne_affinities: d2")
+    d2 = _dense_rows(d2, "tsne_affinities: d2", square=True)
     n = d2.shape[0]
     perplexity = float(perplexity)
     if not 0.0 < perplexity < n:
@@ -926,7 +971,7 @@ def tsne_affinities(d2, perplexity, *, out=None):
     floats = L.lib().pti_tsne_affinities_ws_floats(n)
     if floats <= 0:
         raise ValueError(f"tsne_affinities: unsupported shape {tuple(d2.shape)} (2 <= n <= 8192)")
-    out = _latent_out(out, (n, n), d2, "tsne_affinities")
+    out = _rows_out(out, (n, n), F32, d2.device, "tsne_affinities")
     if out.data_ptr() == d2.data_ptr():
         raise ValueError("tsne_affinities: out must not be d2")
     sums = torch.empty(2, dtype=torch.float64, device=d2.device)
@@ -944,20 +989,16 @@ def tsne_step(p, y_in, y_out, update, gains, record, *, sums, exaggeration, mome
     tensor that receives ``{KL(exaggeration * P || Q) at y_in, |gain * grad|_2}`` when ``with_record`` (an iteration
     without a record skips the fp64 work behind the KL value).
     Runs on the current stream, no host sync; bitwise reproducible."""
-    p = _tsne_matrix(p, "tsne_step: p")
+    p = _dense_rows(p, "tsne_step: p", square=True)
     n = p.shape[0]
     for name, t in (("y_in", y_in), ("y_out", y_out), ("update", update), ("gains", gains)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"tsne_step: {name}: expected a CUDA(HIP) tensor")
-        _chk(t, F32, f"tsne_step: {name}", 2)
+        _tensor(t, F32, f"tsne_step: {name}", 2)
         if t.shape[0] != n or t.device != p.device:
             raise ValueError(f"tsne_step: {name} must be [{n}, 2] on {p.device}, got {tuple(t.shape)}")
         if t.shape[1] != 2:
             raise ValueError(f"tsne_step: {name} has {t.shape[1]} columns; only n_components = 2 is built")
     for name, t in (("record", record), ("sums", sums)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"tsne_step: {name}: expected a CUDA(HIP) tensor")
-        _chk(t, torch.float64, f"tsne_step: {name}", 1)
+        _tensor(t, torch.float64, f"tsne_step: {name}", 1)
         if t.numel() != 2 or t.device != p.device:
             raise ValueError(f"tsne_step: {name} must hold 2 doubles on {p.device}")
     if y_in.data_ptr() == y_out.data_ptr():
@@ -977,7 +1018,6 @@ UmapGraph = namedtuple("UmapGraph", "indptr indices weights rate rho sigma nnz")
 UmapGraph.__doc__ = """The fuzzy graph of ``umap_graph`` as device CSR: ``indptr`` int32 [n + 1]; ``indices`` int32 (ascending
 within a row), ``weights`` fp32 and ``rate`` int32, allocated for min(2 n k, n^2) entries of which the first ``nnz`` are
 written; ``rho`` / ``sigma`` fp32 [n]; ``nnz`` = ``indptr[n]``, a 0-d DEVICE tensor (reading it is a host sync)."""
-I32 = torch.int32
 
 
 def umap_knn(dist, k, *, out=None):
@@ -985,11 +1025,11 @@ def umap_knn(dist, k, *, out=None):
     ``(knn_idx int32 [n, k], knn_dist fp32 [n, k])``, ascending by (distance, column): the diagonal competes like any other
     entry and equal distances go by the lower column.  Exact.  ``out``: a pair of tensors to write into.
     3 <= n <= 8192, 2 <= k <= 256, k < n.  Runs on the current stream, no host sync."""
-    dist = _tsne_matrix(dist, "umap_knn: dist")
+    idx, kd = _outs("umap_knn", out, ("knn_idx", "knn_dist"))
+    dist = _dense_rows(dist, "umap_knn: dist", square=True)
     n, k = dist.shape[0], int(k)
     if not (3 <= n <= 8192 and 2 <= k <= 256 and k < n):
         raise ValueError(f"umap_knn: unsupported shape {tuple(dist.shape)} with k={k} (3 <= n <= 8192, 2 <= k <= 256, k < n)")
-    idx, kd = (None, None) if out is None else out
     idx = _out(idx, (n, k), I32, dist.device, "umap_knn: knn_idx")
     kd = _out(kd, (n, k), F32, dist.device, "umap_knn: knn_dist")
     L.check(L.lib().pti_umap_knn(_ptr(dist), dist.stride(0), n, k, _ptr(idx), _ptr(kd), _stream()), "pti_umap_knn")
@@ -1003,9 +1043,7 @@ def umap_graph(knn_idx, knn_dist, n_epochs):
     ``epochs_per_sample``.  The CSR arrays are allocated for the upper bound min(2 n k, n^2), so nothing comes back to the
     host.  1 <= n_epochs <= 2000.  Runs on the current stream, no host sync; bitwise reproducible."""
     for name, t, dtype in (("knn_idx", knn_idx, I32), ("knn_dist", knn_dist, F32)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"umap_graph: {name}: expected a CUDA(HIP) tensor")
-        _chk(t, dtype, f"umap_graph: {name}", 2)
+        _tensor(t, dtype, f"umap_graph: {name}", 2)
     n, k = knn_idx.shape
     if tuple(knn_dist.shape) != (n, k) or knn_dist.device != knn_idx.device:
         raise ValueError(f"umap_graph: knn_dist must be [{n}, {k}] on {knn_idx.device}, got {tuple(knn_dist.shape)}")
@@ -1034,9 +1072,7 @@ def umap_epoch(graph, y_in, y_out, *, a, b, alpha, epoch, seed, negative_sample_
     Runs on the current stream, no host sync; bitwise reproducible."""
     for name, t, dtype in (("indptr", graph.indptr, I32), ("indices", graph.indices, I32), ("rate", graph.rate, I32),
                            ("y_in", y_in, F32), ("y_out", y_out, F32)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"umap_epoch: {name}: expected a CUDA(HIP) tensor")
-        _chk(t, dtype, f"umap_epoch: {name}", 2 if name[0] == "y" else 1)
+        _tensor(t, dtype, f"umap_epoch: {name}", 2 if name[0] == "y" else 1)
     n = graph.indptr.numel() - 1
     if not 3 <= n <= 8192:
         raise ValueError(f"umap_epoch: unsupported shape: {n} rows (3 <= n <= 8192)")
@@ -1069,9 +1105,7 @@ def _umap_cross_shape(who, m, n, k):
 
 
 def _umap_embedding(who, name, t, rows, device):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
-    _chk(t, F32, f"{who}: {name}", 2)
+    _tensor(t, F32, f"{who}: {name}", 2)
     if (rows is not None and t.shape[0] != rows) or t.device != device:
         raise ValueError(f"{who}: {name} must be [{'n' if rows is None else rows}, 2] on {device}, got {tuple(t.shape)}")
     if t.shape[1] != 2:
@@ -1084,15 +1118,10 @@ def umap_knn_cross(dist, k, *, out=None):
     column); equal distances go by the lower column.  Exact.  A view with a row stride is read in place.  ``out``: a pair
     of tensors to write into.  1 <= m <= 8192, 3 <= n <= 8192, 2 <= k <= 256, k < n.  Runs on the current stream, no host
     sync."""
-    if not isinstance(dist, torch.Tensor) or not dist.is_cuda:
-        raise ValueError("umap_knn_cross: dist: expected a CUDA(HIP) tensor")
-    if dist.dtype != F32:
-        raise TypeError(f"umap_knn_cross: dist: expected fp32, got {dist.dtype}")
-    if dist.dim() != 2 or dist.stride(1) != 1 or dist.stride(0) < dist.shape[1]:
-        raise ValueError(f"umap_knn_cross: dist: expected an [m, n] matrix with dense rows, got {tuple(dist.shape)}")
+    idx, kd = _outs("umap_knn_cross", out, ("knn_idx", "knn_dist"))
+    dist = _dense_rows(dist, "umap_knn_cross: dist")
     (m, n), k = dist.shape, int(k)
     _umap_cross_shape("umap_knn_cross", m, n, k)
-    idx, kd = (None, None) if out is None else out
     idx = _out(idx, (m, k), I32, dist.device, "umap_knn_cross: knn_idx")
     kd = _out(kd, (m, k), F32, dist.device, "umap_knn_cross: knn_dist")
     L.check(L.lib().pti_umap_knn_cross(_ptr(dist), dist.stride(0), m, n, k, _ptr(idx), _ptr(kd), _stream()), "pti_umap_knn_cross")
@@ -1108,9 +1137,7 @@ def umap_transform_graph(knn_idx, knn_dist, y_train, n_epochs):
     host sync; bitwise reproducible."""
     who = "umap_transform_graph"
     for name, t, dtype in (("knn_idx", knn_idx, I32), ("knn_dist", knn_dist, F32)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
-        _chk(t, dtype, f"{who}: {name}", 2)
+        _tensor(t, dtype, f"{who}: {name}", 2)
     m, k = knn_idx.shape
     dev = knn_idx.device
     if tuple(knn_dist.shape) != (m, k) or knn_dist.device != dev:
@@ -1141,9 +1168,7 @@ def umap_transform_layout(tg, y_train, y_in, y_out, *, a, b, n_epochs, seed, sta
     Runs on the current stream, no host sync; bitwise reproducible."""
     who = "umap_transform_layout"
     for name, t in (("indices", tg.indices), ("rate", tg.rate)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
-        _chk(t, I32, f"{who}: {name}", 2)
+        _tensor(t, I32, f"{who}: {name}", 2)
     m, k = tg.indices.shape
     dev = tg.indices.device
     if tuple(tg.rate.shape) != (m, k) or tg.rate.device != dev:
@@ -1211,12 +1236,9 @@ def mask_geometry(src, offsets, hw, *, elem, max_h, sample_rows, bottom_offsets,
         raise ValueError(f"mask_geometry: bottom_offsets must be a vector, got {tuple(bottom_offsets.shape)}")
     samples, n_bottom = sample_rows.shape[1], bottom_offsets.numel()
     shapes = ((b, 4), (b, samples), (b, n_bottom))
-    if out is None:
-        out = (None, None, None)
-    elif len(out) != 3:   # caller-owned outputs (views of larger buffers included)
-        raise ValueError("mask_geometry: out must be (bbox, bbox_widths, bottom_widths)")
+    names = ("bbox", "bbox_widths", "bottom_widths")   # caller-owned outputs (views of larger buffers included)
     bbox, bbox_widths, bottom_widths = (_out(t, sh, torch.int32, src.device, f"mask_geometry: out {name}", rank=False)
-                                        for name, t, sh in zip(("bbox", "bbox_widths", "bottom_widths"), out, shapes))
+                                        for name, t, sh in zip(names, _outs("mask_geometry", out, names), shapes))
     # a table or an output without entries is passed as NULL
     L.check(L.lib().pti_mask_geometry(_ptr(src), _ptr(offsets), _ptr(hw), b, elem, max_h,
                                       _ptr(sample_rows) if samples else None, samples,
@@ -1230,6 +1252,32 @@ def mask_geometry(src, offsets, hw, *, elem, max_h, sample_rows, bottom_offsets,
 MASK_COMPARE_MAX_EDGE = 1024                            # PTI_MASK_COMPARE_MAX_EDGE: the kernel's bound on h and w
 MASK_COMPARE_COLUMNS = L.MASK_COMPARE_COLUMNS              # the int32 columns, in order
 MASK_COMPARE_SUMS = ("sq_err_sum", "max_gt", "max_pred")
+
+
+def _image_pair(who, names, a, b, *, min_edge=1, max_edge=MASK_COMPARE_MAX_EDGE, max_n=65535, optional_b=False):
+    """The common checks of a pair of image batches -> (a, b, n, h, w) as ``[n, h, w]`` views.  ``min_edge`` / ``max_edge``
+    bound h and w; ``max_n=None``: the launcher has no cap on n; ``optional_b``: ``b`` may be ``None`` and stays ``None``."""
+    pair = [(names[0], a)] if optional_b and b is None else list(zip(names, (a, b)))
+    for name, t in pair:
+        if not isinstance(t, torch.Tensor) or t.dtype != F32:
+            raise TypeError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    for name, t in pair:
+        if not t.is_cuda or t.device != a.device:
+            raise ValueError(f"{who}: {name} must be a CUDA(HIP) tensor on the device of {names[0]}")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+    if a.dim() == 4 and a.shape[1] == 1:
+        a = a[:, 0]
+    if b is not None and b.dim() == 4 and b.shape[1] == 1:
+        b = b[:, 0]
+    if a.dim() != 3 or (b is not None and b.shape != a.shape):
+        raise ValueError(f"{who}: expected [n, h, w] or [n, 1, h, w] images of one shape, got {tuple(a.shape)}"
+                         + (f" / {tuple(b.shape)}" if b is not None else ""))
+    n, h, w = a.shape
+    if not (1 <= n <= (max_n or n) and min_edge <= h <= max_edge and min_edge <= w <= max_edge):
+        raise ValueError(f"{who}: unsupported shape {tuple(a.shape)} ({f'1 <= n <= {max_n}' if max_n else 'n >= 1'}, "
+                         f"{min_edge} <= h, w <= {max_edge})")
+    return a, b, n, h, w
 
 
 def mask_compare(gt, pred, *, threshold=0.2, out=None, cleaned=None):
@@ -1248,46 +1296,25 @@ def mask_compare(gt, pred, *, threshold=0.2, out=None, cleaned=None):
     with the results, ``utils.compare_metrics.pair_metrics`` raises on it.  ``out=(counts, sums)`` are written in place.
     Runs on the current stream, no host sync; bitwise reproducible; the scratch buffer is cached per (stream, shape)."""
     who = "mask_compare"
-    for name, t in (("gt", gt), ("pred", pred)):
-        if not isinstance(t, torch.Tensor) or t.dtype != F32:
-            raise TypeError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
-    for name, t in (("gt", gt), ("pred", pred)):
-        if not t.is_cuda or t.device != gt.device:
-            raise ValueError(f"{who}: {name} must be a CUDA(HIP) tensor on the device of gt")
-        if not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be contiguous")
-    if gt.dim() == 4 and gt.shape[1] == 1:
-        gt = gt[:, 0]
-    if pred.dim() == 4 and pred.shape[1] == 1:
-        pred = pred[:, 0]
-    if gt.dim() != 3 or pred.shape != gt.shape:
-        raise ValueError(f"{who}: expected [n, h, w] or [n, 1, h, w] images of one shape, got {tuple(gt.shape)} / {tuple(pred.shape)}")
-    n, h, w = gt.shape
-    if n < 1 or not (1 <= h <= MASK_COMPARE_MAX_EDGE and 1 <= w <= MASK_COMPARE_MAX_EDGE):
-        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)} (n >= 1, 1 <= h, w <= {MASK_COMPARE_MAX_EDGE})")
+    gt, pred, n, h, w = _image_pair(who, ("gt", "pred"), gt, pred, max_n=None)
     threshold = float(threshold)
     if not threshold >= 0.0:
         raise ValueError(f"{who}: threshold must be >= 0, got {threshold}")
-    if out is None:
-        out = (None, None)
-    elif len(out) != 2:
-        raise ValueError(f"{who}: out must be (counts, sums)")
+    out = _outs(who, out, ("counts", "sums"))
     counts = _out(out[0], (n, len(MASK_COMPARE_COLUMNS)), torch.int32, gt.device, f"{who}: out[0] (counts)")
     sums = _out(out[1], (n, len(MASK_COMPARE_SUMS)), torch.float64, gt.device, f"{who}: out[1] (sums)")
-    nbytes = L.lib().pti_mask_compare_ws_bytes(n, h, w)
-    if nbytes <= 0:
-        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)}")
     stream = _stream()
-    ws = _scratch("mask_compare", (n, h, w), (nbytes + 3) // 4, gt.device, stream)
+    ws, ws_bytes = _scratch_bytes(who, "mask_compare", (n, h, w), L.lib().pti_mask_compare_ws_bytes(n, h, w), tuple(gt.shape),
+                                  gt.device, stream)
     if cleaned is None or cleaned is False:
         L.check(L.lib().pti_mask_compare(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(counts), _ptr(sums), _ptr(ws),
-                                         ws.numel() * 4, stream), "pti_mask_compare")
+                                         ws_bytes, stream), "pti_mask_compare")
         return counts, sums
     cleaned = _out(None if cleaned is True else cleaned, (n, h, w), F32, gt.device, f"{who}: cleaned")
     if cleaned.data_ptr() in (gt.data_ptr(), pred.data_ptr()):
         raise ValueError(f"{who}: cleaned must not be gt or pred")
     L.check(L.lib().pti_mask_compare_cleaned(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(counts), _ptr(sums), _ptr(cleaned),
-                                             _ptr(ws), ws.numel() * 4, stream), "pti_mask_compare_cleaned")
+                                             _ptr(ws), ws_bytes, stream), "pti_mask_compare_cleaned")
     return counts, sums, cleaned
 
 
@@ -1307,36 +1334,17 @@ def ssim_uniform(gt, pred, *, data_range=None, out=None):
     An image whose range is 0 reports ``{0, 0}`` (the SSIM is 0 / 0 there).  ``out`` is written in place.  At most three
     launches on the current stream, no host sync; bitwise reproducible; the scratch buffer is cached per (stream, shape)."""
     who = "ssim_uniform"
-    for name, t in (("gt", gt), ("pred", pred)):
-        if not isinstance(t, torch.Tensor) or t.dtype != F32:
-            raise TypeError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
     if data_range is not None:
         data_range = float(data_range)
         if not data_range >= 0.0:
             raise ValueError(f"{who}: data_range must be >= 0 or None, got {data_range}")
-    for name, t in (("gt", gt), ("pred", pred)):
-        if not t.is_cuda or t.device != gt.device:
-            raise ValueError(f"{who}: {name} must be a CUDA(HIP) tensor on the device of gt")
-        if not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be contiguous")
-    if gt.dim() == 4 and gt.shape[1] == 1:
-        gt = gt[:, 0]
-    if pred.dim() == 4 and pred.shape[1] == 1:
-        pred = pred[:, 0]
-    if gt.dim() != 3 or pred.shape != gt.shape:
-        raise ValueError(f"{who}: expected [n, h, w] or [n, 1, h, w] images of one shape, got {tuple(gt.shape)} / {tuple(pred.shape)}")
-    n, h, w = gt.shape
-    lo, hi = SSIM_UNIFORM_MIN_EDGE, MASK_COMPARE_MAX_EDGE
-    if not (1 <= n <= 65535 and lo <= h <= hi and lo <= w <= hi):
-        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)} (1 <= n <= 65535, {lo} <= h, w <= {hi})")
+    gt, pred, n, h, w = _image_pair(who, ("gt", "pred"), gt, pred, min_edge=SSIM_UNIFORM_MIN_EDGE)
     out = _out(out, (n, len(SSIM_UNIFORM_COLUMNS)), torch.float64, gt.device, f"{who}: out")
-    nbytes = L.lib().pti_ssim_uniform_ws_bytes(n, h, w)
-    if nbytes <= 0:
-        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)}")
     stream = _stream()
-    ws = _scratch("ssim_uniform", (n, h, w), (nbytes + 3) // 4, gt.device, stream)
+    ws, ws_bytes = _scratch_bytes(who, "ssim_uniform", (n, h, w), L.lib().pti_ssim_uniform_ws_bytes(n, h, w), tuple(gt.shape),
+                                  gt.device, stream)
     L.check(L.lib().pti_ssim_uniform(_ptr(gt), _ptr(pred), n, h, w, -1.0 if data_range is None else data_range, _ptr(out),
-                                     _ptr(ws), ws.numel() * 4, stream), "pti_ssim_uniform")
+                                     _ptr(ws), ws_bytes, stream), "pti_ssim_uniform")
     return out
 
 
@@ -1345,36 +1353,6 @@ MASK_MOMENTS_COLUMNS = L.MASK_MOMENTS_COLUMNS              # int64 columns per (
 MASK_MOMENTS_COEFFS = ("beta", "cos_beta", "sin_beta")     # fp64 per (image, side)
 ALIGN_BOTTOM_COLUMNS = L.ALIGN_BOTTOM_COLUMNS              # int32 columns per image
 ALIGN_BOTTOM_MIN_HEIGHT = 5                                # below it there is no bottom fifth
-
-
-def _image_pair(who, names, a, b):
-    """The common checks of a pair of image batches -> (a, b, n, h, w) as ``[n, h, w]`` views."""
-    for name, t in zip(names, (a, b)):
-        if not isinstance(t, torch.Tensor) or t.dtype != F32:
-            raise TypeError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
-    for name, t in zip(names, (a, b)):
-        if not t.is_cuda or t.device != a.device:
-            raise ValueError(f"{who}: {name} must be a CUDA(HIP) tensor on the device of {names[0]}")
-        if not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be contiguous")
-    if a.dim() == 4 and a.shape[1] == 1:
-        a = a[:, 0]
-    if b.dim() == 4 and b.shape[1] == 1:
-        b = b[:, 0]
-    if a.dim() != 3 or b.shape != a.shape:
-        raise ValueError(f"{who}: expected [n, h, w] or [n, 1, h, w] images of one shape, got {tuple(a.shape)} / {tuple(b.shape)}")
-    n, h, w = a.shape
-    if not (1 <= n <= 65535 and 1 <= h <= MASK_COMPARE_MAX_EDGE and 1 <= w <= MASK_COMPARE_MAX_EDGE):
-        raise ValueError(f"{who}: unsupported shape {tuple(a.shape)} (1 <= n <= 65535, 1 <= h, w <= {MASK_COMPARE_MAX_EDGE})")
-    return a, b, n, h, w
-
-
-def _outs(who, out, names):
-    if out is None:
-        return (None,) * len(names)
-    if len(out) != len(names):
-        raise ValueError(f"{who}: out must be ({', '.join(names)})")
-    return tuple(out)
 
 
 def mask_moments(gt, pred, *, threshold=0.2, out=None):
@@ -1396,13 +1374,11 @@ def mask_moments(gt, pred, *, threshold=0.2, out=None):
     cleaned = _out(out[0], (n, h, w), F32, gt.device, f"{who}: out[0] (cleaned)")
     moments = _out(out[1], (n, 2, len(MASK_MOMENTS_COLUMNS)), torch.int64, gt.device, f"{who}: out[1] (moments)")
     coeffs = _out(out[2], (n, 2, 3), torch.float64, gt.device, f"{who}: out[2] (coeffs)")
-    nbytes = L.lib().pti_mask_moments_ws_bytes(n, h, w)
-    if nbytes <= 0:
-        raise ValueError(f"{who}: unsupported shape {tuple(gt.shape)}")
     stream = _stream()
-    ws = _scratch("mask_moments", (n, h, w), (nbytes + 3) // 4, gt.device, stream)
+    ws, ws_bytes = _scratch_bytes(who, "mask_moments", (n, h, w), L.lib().pti_mask_moments_ws_bytes(n, h, w), tuple(gt.shape),
+                                  gt.device, stream)
     L.check(L.lib().pti_mask_moments(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(cleaned), _ptr(moments), _ptr(coeffs),
-                                     _ptr(ws), ws.numel() * 4, stream), "pti_mask_moments")
+                                     _ptr(ws), ws_bytes, stream), "pti_mask_moments")
     return cleaned, moments, coeffs
 
 
@@ -1478,9 +1454,6 @@ def display_planes(a, b=None, *, nsrc=None, low=2, high=98, rot90=0, dtype=torch
     ``stats``: float64 ``[n, nsrc, 3]`` = ``{non-zero count, p_low, p_high}`` on the device.  Inputs must be finite.  Runs
     on the current stream, no host sync, no scratch (one workgroup per plane keeps everything in LDS)."""
     who = "display_planes"
-    for name, t in (("a", a), ("b", b)):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != F32):
-            raise TypeError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
     if nsrc is None:
         nsrc = 1 if b is None else 2
     if nsrc not in (1, 2, 3):
@@ -1495,24 +1468,10 @@ def display_planes(a, b=None, *, nsrc=None, low=2, high=98, rot90=0, dtype=torch
         raise ValueError(f"{who}: rot90 must be 0, 1, 2 or 3, got {rot90}")
     if dtype not in (torch.uint8, F32):
         raise TypeError(f"{who}: dtype must be torch.uint8 or torch.float32, got {dtype}")
-    if a.dim() == 4 and a.shape[1] == 1:
-        a = a[:, 0]
-    if b is not None and b.dim() == 4 and b.shape[1] == 1:
-        b = b[:, 0]
-    if a.dim() != 3 or (b is not None and b.shape != a.shape):
-        raise ValueError(f"{who}: expected [n, h, w] or [n, 1, h, w] images of one shape, got {tuple(a.shape)}"
-                         + (f" / {tuple(b.shape)}" if b is not None else ""))
+    a, b, n, h, w = _image_pair(who, ("a", "b"), a, b, max_edge=DISPLAY_MAX_EDGE, max_n=DISPLAY_MAX_PLANES // nsrc,
+                                optional_b=True)
     if nsrc == 1:
         b = None
-    _chk(a, F32, f"{who}: a")
-    if b is not None:
-        _chk(b, F32, f"{who}: b")
-        if b.device != a.device:
-            raise ValueError(f"{who}: a and b must be on one device")
-    n, h, w = a.shape
-    if n < 1 or not (1 <= h <= DISPLAY_MAX_EDGE and 1 <= w <= DISPLAY_MAX_EDGE) or n * nsrc > DISPLAY_MAX_PLANES:
-        raise ValueError(f"{who}: unsupported shape {tuple(a.shape)} with nsrc = {nsrc} (1 <= h, w <= {DISPLAY_MAX_EDGE}, "
-                         f"1 <= n * nsrc <= {DISPLAY_MAX_PLANES})")
     ho, wo = (w, h) if rot90 & 1 else (h, w)
     canvas = torch.empty((n, ho, nsrc * wo), dtype=dtype, device=a.device)
     stats = torch.empty((n, nsrc, 3), dtype=torch.float64, device=a.device)
@@ -1545,45 +1504,25 @@ def rank_agreement(z, attrs, channels, deltas, *, out=None):
     ``out=(counts, loss_sum)`` are written in place.  2 <= N <= 32768, L <= 16, na <= 16; inputs must be finite.  Runs on
     the current stream, no host sync; bitwise reproducible; the scratch buffer is cached per (stream, shape)."""
     who = "rank_agreement"
-    for name, t in (("z", z), ("attrs", attrs)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
-        if not t.is_floating_point():
-            raise TypeError(f"{who}: {name}: expected a floating-point matrix, got {t.dtype}")
-        if t.dim() != 2:
-            raise ValueError(f"{who}: {name}: expected a matrix, got {tuple(t.shape)}")
-    n, l = z.shape
-    na = attrs.shape[0]
-    if attrs.shape[1] != n or attrs.device != z.device:
-        raise ValueError(f"{who}: z {tuple(z.shape)} needs attrs [na, {n}] on {z.device}, got {tuple(attrs.shape)} on {attrs.device}")
+    out = _outs(who, out, ("counts", "loss_sum"))
+    zt, attrs, n, l, na, ldz, lda = _latent_attrs(who, z, attrs)
     if not (2 <= n <= RANK_AGREEMENT_MAX_N and 1 <= l <= RANK_AGREEMENT_MAX_L and 1 <= na <= RANK_AGREEMENT_MAX_NA):
         raise ValueError(f"{who}: unsupported shape z {tuple(z.shape)} attrs {tuple(attrs.shape)} (2 <= N <= {RANK_AGREEMENT_MAX_N}, "
                          f"1 <= L <= {RANK_AGREEMENT_MAX_L}, 1 <= na <= {RANK_AGREEMENT_MAX_NA})")
-    zt = z.t()                                               # [L, N]: the kernel reads channel-major rows
-    if zt.dtype != F32:
-        zt = zt.to(F32)
-    if zt.stride(1) != 1 or zt.stride(0) < n:
-        zt = zt.contiguous()
-    attrs = _rows(attrs, f"{who}: attrs")
     channels = [int(v) for v in (channels.tolist() if isinstance(channels, torch.Tensor) else channels)]
     deltas = [float(v) for v in (deltas.tolist() if isinstance(deltas, torch.Tensor) else deltas)]
     if len(channels) != na or len(deltas) != na:
         raise ValueError(f"{who}: channels / deltas must hold one value per attribute ({na}), got {len(channels)} / {len(deltas)}")
     if any(c >= l for c in channels):
         raise ValueError(f"{who}: channels {channels} must lie below the {l} latent channels")
-    if out is None:
-        out = (None, None)
     counts = _out(out[0], (na, l, 5), I64, z.device, f"{who}: out[0] (counts)")
     loss_sum = _out(out[1], (na,), torch.float64, z.device, f"{who}: out[1] (loss_sum)")
-    nbytes = L.lib().pti_rank_agreement_ws_bytes(n, l, na)
-    if nbytes <= 0:
-        raise ValueError(f"{who}: unsupported shape z {tuple(z.shape)} attrs {tuple(attrs.shape)}")
     stream = _stream()
-    ws = _scratch("rank", (n, l, na), (nbytes + 3) // 4, z.device, stream)
-    ldz, lda = (zt.stride(0) if l > 1 else n), (attrs.stride(0) if na > 1 else n)   # a single row's stride means nothing
+    ws, ws_bytes = _scratch_bytes(who, "rank", (n, l, na), L.lib().pti_rank_agreement_ws_bytes(n, l, na),
+                                  f"z {tuple(z.shape)} attrs {tuple(attrs.shape)}", z.device, stream)
     L.check(L.lib().pti_rank_agreement(_ptr(zt), ldz, _ptr(attrs), lda, n, l, na,
                                        (C.c_int32 * na)(*channels), (C.c_float * na)(*deltas), _ptr(counts), _ptr(loss_sum),
-                                       _ptr(ws), ws.numel() * 4, stream), "pti_rank_agreement")
+                                       _ptr(ws), ws_bytes, stream), "pti_rank_agreement")
     return counts, loss_sum
 
 
@@ -1599,7 +1538,7 @@ def tied_ranks(cols, *, out=None):
     #{j: x_j == x_i} + 1``, exactly ``2 * scipy.stats.rankdata(x, "average")``; ``-0.0`` ties with ``0.0``.  ``out`` is
     written in place.  2 <= N <= 32768, 1 <= M <= 32; inputs must be finite.  Current stream, no host sync, exact."""
     who = "tied_ranks"
-    cols = _rows(cols, f"{who}: cols")
+    cols = _dense_rows(cols, f"{who}: cols", copy=True)
     m, n = cols.shape
     if not (2 <= n <= DISENT_MAX_N and 1 <= m <= DISENT_MAX_COLS):
         raise ValueError(f"{who}: unsupported shape cols {tuple(cols.shape)} (2 <= N <= {DISENT_MAX_N}, 1 <= M <= {DISENT_MAX_COLS})")
@@ -1617,17 +1556,11 @@ def rank_moments(rank2, *, out=None):
     and int64 ``[M, M]`` device tensors, ``gram[a, b] = sum_i rank2[a, i] * rank2[b, i]`` in 64-bit integers: exact.
     ``rank2``: contiguous int32 ``[M, N]``.  ``out=(sums, gram)`` are written in place.  Current stream, no host sync."""
     who = "rank_moments"
-    if not isinstance(rank2, torch.Tensor) or not rank2.is_cuda:
-        raise ValueError(f"{who}: rank2: expected a CUDA(HIP) tensor")
-    if rank2.dtype != torch.int32:
-        raise TypeError(f"{who}: rank2: expected torch.int32, got {rank2.dtype}")
-    if rank2.dim() != 2 or not rank2.is_contiguous():
-        raise ValueError(f"{who}: rank2: expected a contiguous [M, N] matrix, got {tuple(rank2.shape)} strides {rank2.stride()}")
+    out = _outs(who, out, ("sums", "gram"))
+    _tensor(rank2, I32, f"{who}: rank2", 2)
     m, n = rank2.shape
     if not (2 <= n <= DISENT_MAX_N and 1 <= m <= DISENT_MAX_COLS):
         raise ValueError(f"{who}: unsupported shape rank2 {tuple(rank2.shape)} (2 <= N <= {DISENT_MAX_N}, 1 <= M <= {DISENT_MAX_COLS})")
-    if out is None:
-        out = (None, None)
     sums = _out(out[0], (m,), I64, rank2.device, f"{who}: out[0] (sums)")
     gram = _out(out[1], (m, m), I64, rank2.device, f"{who}: out[1] (gram)")
     prof = KERNEL_PROFILE
@@ -1662,17 +1595,8 @@ def joint_histogram(z, attrs, edges_z, edges_a, *, out=None):
     device result back (one host synchronisation per call).  2 <= N <= 32768, L <= 16, na <= 16, 2 <= B <= 32.  Runs on
     the current stream; bitwise reproducible; the scratch buffer is cached per (stream, shape)."""
     who = "joint_histogram"
-    for name, t in (("z", z), ("attrs", attrs)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
-        if not t.is_floating_point():
-            raise TypeError(f"{who}: {name}: expected a floating-point matrix, got {t.dtype}")
-        if t.dim() != 2:
-            raise ValueError(f"{who}: {name}: expected a matrix, got {tuple(t.shape)}")
-    n, l = z.shape
-    na = attrs.shape[0]
-    if attrs.shape[1] != n or attrs.device != z.device:
-        raise ValueError(f"{who}: z {tuple(z.shape)} needs attrs [na, {n}] on {z.device}, got {tuple(attrs.shape)} on {attrs.device}")
+    out = _outs(who, out, ("bins_z", "bins_a", "counts"))
+    zt, attrs, n, l, na, ldz, lda = _latent_attrs(who, z, attrs)
     edges_z = torch.as_tensor(edges_z)
     bins = int(edges_z.shape[1]) if edges_z.dim() == 2 else 0
     if not (2 <= n <= DISENT_MAX_N and 1 <= l <= 16 and 1 <= na <= 16 and 2 <= bins <= DISENT_MAX_BINS):
@@ -1680,32 +1604,22 @@ def joint_histogram(z, attrs, edges_z, edges_a, *, out=None):
                          f"{DISENT_MAX_N}, 1 <= L <= 16, 1 <= na <= 16, 2 <= B <= {DISENT_MAX_BINS})")
     edges_z = _edges(edges_z, l, bins, z.device, f"{who}: edges_z")
     edges_a = _edges(edges_a, na, bins, z.device, f"{who}: edges_a")
-    zt = z.t()                                               # [L, N]: the kernel reads channel-major rows
-    if zt.dtype != F32:
-        zt = zt.to(F32)
-    if zt.stride(1) != 1 or zt.stride(0) < n:
-        zt = zt.contiguous()
-    attrs = _rows(attrs, f"{who}: attrs")
     low = torch.cat([zt.amin(1).double() < edges_z[:, 0], attrs.amin(1).double() < edges_a[:, 0]])
     if bool(low.any()):                                      # the host synchronisation of this wrapper
         col = int(low.nonzero()[0])
         raise ValueError(f"{who}: {'channel ' + str(col) if col < l else 'attribute ' + str(col - l)} holds a value below its "
                          "first edge: it has no bin")
-    if out is None:
-        out = (None, None, None)
     bins_z = _out(out[0], (l, n), torch.uint8, z.device, f"{who}: out[0] (bins_z)")
     bins_a = _out(out[1], (na, n), torch.uint8, z.device, f"{who}: out[1] (bins_a)")
     counts = _out(out[2], (na, l, bins, bins), torch.int32, z.device, f"{who}: out[2] (counts)")
-    nbytes = L.lib().pti_joint_histogram_ws_bytes(n, l, na, bins)
-    if nbytes <= 0:
-        raise ValueError(f"{who}: unsupported shape z {tuple(z.shape)} attrs {tuple(attrs.shape)} bins {bins}")
     stream = _stream()
-    ws = _scratch("jhist", (n, l, na, bins), (nbytes + 3) // 4, z.device, stream)
-    ldz, lda = (zt.stride(0) if l > 1 else n), (attrs.stride(0) if na > 1 else n)   # a single row's stride means nothing
+    nbytes = L.lib().pti_joint_histogram_ws_bytes(n, l, na, bins)
+    ws, ws_bytes = _scratch_bytes(who, "jhist", (n, l, na, bins), nbytes,
+                                  f"z {tuple(z.shape)} attrs {tuple(attrs.shape)} bins {bins}", z.device, stream)
     prof = KERNEL_PROFILE
     rec = None if prof is None else _prof_begin(prof)
     L.check(L.lib().pti_joint_histogram(_ptr(zt), ldz, _ptr(attrs), lda, n, l, na, bins, _ptr(edges_z), _ptr(edges_a),
-                                        _ptr(bins_z), _ptr(bins_a), _ptr(counts), _ptr(ws), ws.numel() * 4, stream),
+                                        _ptr(bins_z), _ptr(bins_a), _ptr(counts), _ptr(ws), ws_bytes, stream),
             "pti_joint_histogram")
     if rec is not None:   # the values once, the bin indices once per partner column, the partial tables twice
         _prof_end(rec, 0.0, 5.0 * n * (l + na) + 2.0 * n * l * na + 2.0 * nbytes + 4.0 * counts.numel(),
@@ -1732,40 +1646,22 @@ def ksg_counts(z, attrs, k, *, out=None):
     one check that reads a device result back (one host synchronisation per call).  Runs on the current stream; exact,
     bitwise reproducible, no scratch buffer."""
     who = "ksg_counts"
-    for name, t in (("z", z), ("attrs", attrs)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
-        if not t.is_floating_point():
-            raise TypeError(f"{who}: {name}: expected a floating-point matrix, got {t.dtype}")
-        if t.dim() != 2:
-            raise ValueError(f"{who}: {name}: expected a matrix, got {tuple(t.shape)}")
+    out = _outs(who, out, ("eps", "nx", "ny"))
     if isinstance(k, bool) or not isinstance(k, int):
         raise TypeError(f"{who}: k: expected an int, got {type(k).__name__}")
-    n, l = z.shape
-    na = attrs.shape[0]
-    if attrs.shape[1] != n or attrs.device != z.device:
-        raise ValueError(f"{who}: z {tuple(z.shape)} needs attrs [na, {n}] on {z.device}, got {tuple(attrs.shape)} on {attrs.device}")
+    zt, attrs, n, l, na, ldz, lda = _latent_attrs(who, z, attrs)
     if not 1 <= k <= KSG_MAX_K:
         raise ValueError(f"{who}: k = {k} out of range (1 <= k <= {KSG_MAX_K})")
     if not (k + 1 <= n <= KSG_MAX_N and 1 <= l <= RANK_AGREEMENT_MAX_L and 1 <= na <= RANK_AGREEMENT_MAX_NA):
         raise ValueError(f"{who}: unsupported shape z {tuple(z.shape)} attrs {tuple(attrs.shape)} k {k} (k + 1 <= N <= {KSG_MAX_N}, "
                          f"1 <= L <= {RANK_AGREEMENT_MAX_L}, 1 <= na <= {RANK_AGREEMENT_MAX_NA})")
-    zt = z.t()                                               # [L, N]: the kernel reads channel-major rows
-    if zt.dtype != F32:
-        zt = zt.to(F32)
-    if zt.stride(1) != 1 or zt.stride(0) < n:
-        zt = zt.contiguous()
-    attrs = _rows(attrs, f"{who}: attrs")
     bad = torch.cat([~torch.isfinite(zt).all(1), ~torch.isfinite(attrs).all(1)])
     if bool(bad.any()):                                      # the host synchronisation of this wrapper
         col = int(bad.nonzero()[0])
         raise ValueError(f"{who}: {'channel ' + str(col) if col < l else 'attribute ' + str(col - l)} holds a non-finite value")
-    if out is None:
-        out = (None, None, None)
     eps = _out(out[0], (na, l, n), F32, z.device, f"{who}: out[0] (eps)")
     nx = _out(out[1], (na, l, n), torch.int32, z.device, f"{who}: out[1] (nx)")
     ny = _out(out[2], (na, l, n), torch.int32, z.device, f"{who}: out[2] (ny)")
-    ldz, lda = (zt.stride(0) if l > 1 else n), (attrs.stride(0) if na > 1 else n)   # a single row's stride means nothing
     prof = KERNEL_PROFILE
     rec = None if prof is None else _prof_begin(prof)
     L.check(L.lib().pti_ksg_counts(_ptr(zt), ldz, _ptr(attrs), lda, n, l, na, k, _ptr(eps), _ptr(nx), _ptr(ny), _stream()),
@@ -1789,12 +1685,12 @@ def projection_distances(y, *, out=None):
     distances a few units in the last place apart by its rounding).  Symmetric bit for bit with a zero diagonal.  A
     row-strided ``y`` and an ``out`` view with a row stride are used in place.  1 <= n <= 8192.  Runs on the current stream,
     no host sync."""
-    y = _rows(y, "projection_distances: y")
+    y = _dense_rows(y, "projection_distances: y", copy=True)
     n, d = y.shape
     if not (1 <= n <= NEIGHBOR_RANKS_MAX_N and 1 <= d <= PROJECTION_MAX_COLS):
         raise ValueError(f"projection_distances: unsupported shape {tuple(y.shape)} (1 <= n <= {NEIGHBOR_RANKS_MAX_N}, "
                          f"1 <= d <= {PROJECTION_MAX_COLS})")
-    out = _latent_out(out, (n, n), y, "projection_distances")
+    out = _rows_out(out, (n, n), F32, y.device, "projection_distances")
     L.check(L.lib().pti_projection_distances(_ptr(y), y.stride(0), n, d, _ptr(out), out.stride(0), _stream()),
             "pti_projection_distances")
     return out
@@ -1808,10 +1704,8 @@ def neighbor_ranks(dist, nbr_idx, *, out=None):
     allowed); ``nbr_idx`` int32 ``[n, m]`` contiguous.  3 <= n <= 8192, 1 <= m <= 256.  Integers only: exact; a row of the
     result depends on that row of ``dist`` and of ``nbr_idx`` alone.  Runs on the current stream, no host sync."""
     who = "neighbor_ranks"
-    dist = _tsne_matrix(dist, f"{who}: dist")
-    if not isinstance(nbr_idx, torch.Tensor):
-        raise ValueError(f"{who}: nbr_idx: expected a CUDA(HIP) tensor")
-    _chk(nbr_idx, I32, f"{who}: nbr_idx", 2)
+    dist = _dense_rows(dist, f"{who}: dist", square=True)
+    _tensor(nbr_idx, I32, f"{who}: nbr_idx", 2)
     n, m = dist.shape[0], nbr_idx.shape[1]
     if nbr_idx.shape[0] != n or nbr_idx.device != dist.device:
         raise ValueError(f"{who}: nbr_idx must be [{n}, m] on {dist.device}, got {tuple(nbr_idx.shape)} on {nbr_idx.device}")
@@ -1833,19 +1727,12 @@ def segment_row_sums(dist, seg, *, out=None):
     one order that depends on the segment's length alone: the bits of an entry depend on its row and its segment, not on
     ``n``, ``G`` or the launch.  An empty segment gives 0.0.  3 <= n <= 8192, 1 <= G <= 2048.  Runs on the current stream."""
     who = "segment_row_sums"
-    dist = _tsne_matrix(dist, f"{who}: dist")
+    dist = _dense_rows(dist, f"{who}: dist", square=True)
     n = dist.shape[0]
-    if isinstance(seg, torch.Tensor):
-        if seg.dtype != I32:
-            raise TypeError(f"{who}: seg must be int32, got {seg.dtype}")
-        if seg.dim() != 1 or not seg.is_contiguous():
-            raise ValueError(f"{who}: seg must be a contiguous vector of G + 1 offsets")
-        if seg.is_cuda and seg.device != dist.device:
-            raise ValueError(f"{who}: seg must be on {dist.device}")
-        host = seg.tolist()
-    else:
-        host = [int(v) for v in seg]
-        seg = torch.tensor(host, dtype=I32)
+    if not isinstance(seg, torch.Tensor):
+        seg = torch.tensor([int(v) for v in seg], dtype=I32)
+    _offsets(who, "seg", seg, dist.device, "G", host=True)
+    host = seg.tolist()
     g = len(host) - 1
     if not (3 <= n <= NEIGHBOR_RANKS_MAX_N and 1 <= g <= SEGMENT_ROW_SUMS_MAX_G):
         raise ValueError(f"{who}: unsupported shape dist {tuple(dist.shape)} with {g} segments "
@@ -1854,10 +1741,7 @@ def segment_row_sums(dist, seg, *, out=None):
         raise ValueError(f"{who}: seg must ascend from 0 to n = {n}, got {host[0]} .. {host[-1]}")
     if not seg.is_cuda:
         seg = seg.to(dist.device)
-    if out is None:
-        out = torch.empty((n, g), dtype=torch.float64, device=dist.device)
-    else:
-        out = _out(out, (n, g), torch.float64, dist.device, f"{who}: out")
+    out = _out(out, (n, g), torch.float64, dist.device, f"{who}: out")
     L.check(L.lib().pti_segment_row_sums(_ptr(dist), dist.stride(0), n, _ptr(seg), g, _ptr(out), _stream()),
             "pti_segment_row_sums")
     return out
@@ -1865,18 +1749,11 @@ def segment_row_sums(dist, seg, *, out=None):
 
 # ---- co-ranking curves and the Shepard figure (csrc/coranking.hip; include/pti_vae.h "co-ranking curves") --------------
 CORANKING_MIN_N, CORANKING_MAX_N, SHEPARD_MIN_BINS, SHEPARD_MAX_BINS = 4, 8192, 2, 128
-I16 = torch.int16
 
 
 def _coranking_rows(t, dtype, name):
     """A device matrix [m, n] of ``dtype`` with dense rows and 4 <= n <= 8192, 1 <= m <= n, used in place."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
-    if t.dtype != dtype:
-        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
-    if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        raise ValueError(f"{name}: expected an [m, n] matrix with dense rows, got {tuple(t.shape)}")
-    m, n = t.shape
+    m, n = _dense_rows(t, name, dtype).shape
     if not (CORANKING_MIN_N <= n <= CORANKING_MAX_N and 1 <= m <= n):
         raise ValueError(f"{name}: unsupported shape {tuple(t.shape)} ({CORANKING_MIN_N} <= n <= {CORANKING_MAX_N} columns, "
                          f"1 <= m <= n rows)")
@@ -1897,12 +1774,7 @@ def full_ranks(dist, row_offset=0, *, out=None):
     row_offset = int(row_offset)
     if not 0 <= row_offset <= n - m:
         raise ValueError(f"{who}: rows {row_offset} .. {row_offset + m - 1} are outside the matrix of {n} rows")
-    if out is None:
-        out = torch.empty((m, n), dtype=I16, device=dist.device)
-    else:
-        _coranking_rows(out, I16, f"{who}: out")
-        if tuple(out.shape) != (m, n) or out.device != dist.device:
-            raise ValueError(f"{who}: out must be [{m}, {n}] on {dist.device}")
+    out = _rows_out(out, (m, n), I16, dist.device, who)
     L.check(L.lib().pti_full_ranks(_ptr(dist), dist.stride(0), m, n, row_offset, _ptr(out), out.stride(0), _stream()),
             "pti_full_ranks")
     return out
@@ -1941,7 +1813,8 @@ def shepard_fold(dist_high, dist_low, bins=64, *, hist=None):
     by torch, since the library's own division is not correctly rounded; bin ``b`` covers ``[b / scale, (b + 1) / scale)``.
     4 <= n <= 8192, 2 <= bins <= 128.  Runs on the current stream, no host sync."""
     who = "shepard_fold"
-    dist_high, dist_low = _tsne_matrix(dist_high, f"{who}: dist_high"), _tsne_matrix(dist_low, f"{who}: dist_low")
+    dist_high = _dense_rows(dist_high, f"{who}: dist_high", square=True)
+    dist_low = _dense_rows(dist_low, f"{who}: dist_low", square=True)
     n, bins = dist_high.shape[0], int(bins)
     if tuple(dist_low.shape) != (n, n) or dist_low.device != dist_high.device:
         raise ValueError(f"{who}: dist_low must be [{n}, {n}] on {dist_high.device}, got {tuple(dist_low.shape)}")
@@ -2385,7 +2258,7 @@ def mlp_head_fwd(x, params, dims, act, *, mean=None, std=None, targets=None, los
     ``rowloss[i] = sum_t loss(out[i, t], (targets[i, t] - mean[t]) / std[t])`` (``loss``: "mse" or "smooth_l1"), the loss
     on the normalised scale.  Row ``i`` of both depends on row ``i`` only, bit for bit.  Runs on the current stream, no
     host sync; the scratch buffer is cached per (stream, shape).  An unsupported head (``mlp_head_supported``) raises."""
-    x = _rows(x, "mlp_head_fwd: x")
+    x = _dense_rows(x, "mlp_head_fwd: x", copy=True)
     n, d = x.shape
     dims = [int(v) for v in dims]
     if len(dims) < 2 or dims[0] != d:

@@ -67,13 +67,29 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 
 
 def test_workspace_size_constants_match_header():
-    """ops sizes the scratch of the fixed-order reductions from the header's block caps."""
-    from pti_ldm_vae_amd import ops
+    """ops sizes the scratch of the fixed-order reductions from the header's block caps; every other numeric
+    ``#define PTI_*`` that Python repeats by hand (_lib.py, ops.py) holds the header's value too."""
+    from pti_ldm_vae_amd import _lib, ops
     text = open(os.path.join(ROOT, "include", "pti_vae.h")).read()
     caps = {k: int(v) for k, v in re.findall(r"#define (PTI_[A-Z_]+_MAX_BLOCKS) (\d+)", text)}
     assert caps == {"PTI_POST_QUANT_BWD_MAX_BLOCKS": ops.POST_QUANT_BWD_MAX_BLOCKS,
                     "PTI_LATENT_BWD_MAX_BLOCKS": ops.LATENT_BWD_MAX_BLOCKS,
                     "PTI_VAE_LOSS_MAX_BLOCKS": ops.VAE_LOSS_MAX_BLOCKS}
+    defines = {k: int(v) for k, v in re.findall(r"#define (PTI_[A-Z0-9_]+)[ \t]+(\d+)\b", text)}
+    mirrored = {"PTI_ABI_VERSION": _lib.ABI_VERSION,
+                "PTI_DIRECT_REPACK_MAX": _lib.DIRECT_REPACK_MAX,
+                "PTI_WGRAD_BATCH_MAX": _lib.WGRAD_BATCH_MAX,
+                "PTI_MLP_MAX_LAYERS": ops.MLP_MAX_LAYERS,
+                "PTI_MLP_MAX_WIDTH": ops.MLP_MAX_WIDTH,
+                "PTI_MLP_MAX_OUT": ops.MLP_MAX_OUT,
+                "PTI_ELASTIC_MAX_RADIUS": ops.ELASTIC_MAX_RADIUS,
+                "PTI_MASK_COMPARE_MAX_EDGE": ops.MASK_COMPARE_MAX_EDGE,
+                "PTI_MASK_COMPARE_COLUMNS": len(_lib.MASK_COMPARE_COLUMNS),
+                "PTI_MASK_MOMENTS_COLUMNS": len(_lib.MASK_MOMENTS_COLUMNS),
+                "PTI_ALIGN_BOTTOM_COLUMNS": len(_lib.ALIGN_BOTTOM_COLUMNS)}
+    assert {k: defines.get(k) for k in mirrored} == mirrored
+    assert ops.MASK_COMPARE_COLUMNS is _lib.MASK_COMPARE_COLUMNS and ops.MASK_MOMENTS_COLUMNS is _lib.MASK_MOMENTS_COLUMNS
+    assert ops.ALIGN_BOTTOM_COLUMNS is _lib.ALIGN_BOTTOM_COLUMNS
 
 
 def test_tile_and_block_queries_need_no_gpu():

@@ -241,3 +241,14 @@ def test_rank_agreement_refusals_and_size_query():
     assert call(nbytes=ws(100, 4, 2) - 1) == -1 and b"workspace" in h.pti_last_error_string()
     with pytest.raises(L.PtiError):
         L.check(-1, "pti_rank_agreement")
+
+
+def test_rank_agreement_refuses_an_out_tuple_of_the_wrong_length():
+    """The length of ``out=(counts, loss_sum)`` is checked before anything else, so no device is needed."""
+    import torch
+
+    from pti_ldm_vae_amd import ops
+    z, a = torch.zeros(10, 3), torch.zeros(2, 10)
+    for out in ((None,), (None, None, None), ()):
+        with pytest.raises(ValueError, match=r"rank_agreement: out must be \(counts, loss_sum\)"):
+            ops.rank_agreement(z, a, [0, 1], [1.0, 1.0], out=out)

@@ -318,3 +318,18 @@ def test_entry_point_refusals_and_size_query():
     assert hist(nbytes=ws(100, 4, 2, 20) - 1) == -1 and b"workspace" in h.pti_last_error_string()
     with pytest.raises(L.PtiError):
         L.check(-2, "pti_joint_histogram")
+
+
+def test_out_tuples_of_the_wrong_length_are_refused():
+    """``out=(sums, gram)`` / ``out=(bins_z, bins_a, counts)``: the length is checked before anything else (no device needed)."""
+    import torch
+
+    from pti_ldm_vae_amd import ops
+    rank2 = torch.ones(2, 10, dtype=torch.int32)
+    for out in ((None,), (None, None, None)):
+        with pytest.raises(ValueError, match=r"rank_moments: out must be \(sums, gram\)"):
+            ops.rank_moments(rank2, out=out)
+    z, a, ez, ea = torch.rand(10, 3), torch.rand(2, 10), torch.zeros(3, 4), torch.zeros(2, 4)
+    for out in ((None, None), (None, None, None, None)):
+        with pytest.raises(ValueError, match=r"joint_histogram: out must be \(bins_z, bins_a, counts\)"):
+            ops.joint_histogram(z, a, ez, ea, out=out)

@@ -310,3 +310,14 @@ def test_entry_point_refusals():
     for kw in (dict(zt=C.c_void_p(4098)), dict(attrs=C.c_void_p(4098)), dict(eps=C.c_void_p(4098)), dict(nx=C.c_void_p(4097)),
                dict(ny=C.c_void_p(4099))):
         assert ksg(**kw) == -1 and b"misaligned" in h.pti_last_error_string(), kw
+
+
+def test_ksg_counts_refuses_an_out_tuple_of_the_wrong_length():
+    """The length of ``out=(eps, nx, ny)`` is checked before anything else, so no device is needed."""
+    import torch
+
+    from pti_ldm_vae_amd import ops
+    z, a = torch.rand(10, 3), torch.rand(2, 10)
+    for out in ((None, None), (None, None, None, None)):
+        with pytest.raises(ValueError, match=r"ksg_counts: out must be \(eps, nx, ny\)"):
+            ops.ksg_counts(z, a, 3, out=out)

@@ -238,6 +238,14 @@ def test_ops_refuse_cpu_tensors_and_bad_shapes():
         ops.umap_epoch(g, y, y.clone(), a=0.58, b=1.33, alpha=1.0, epoch=0, seed=1)
 
 
+def test_umap_knn_refuses_an_out_tuple_of_the_wrong_length():
+    """The length of ``out=(knn_idx, knn_dist)`` is checked before anything else, so no device is needed."""
+    from pti_ldm_vae_amd import ops
+    for out in ((None,), (None, None, None)):
+        with pytest.raises(ValueError, match=r"umap_knn: out must be \(knn_idx, knn_dist\)"):
+            ops.umap_knn(torch.rand(8, 8), 3, out=out)
+
+
 # ---- API and CLI -------------------------------------------------------------------------------------------------------------
 ARGV = ["--vae-weights", "w.pth", "--config-file", "c.json", "--folder-edente", "e"]
 

@@ -223,6 +223,14 @@ def test_ops_refuse_cpu_tensors():
         ops.umap_transform_layout(tg, torch.rand(8, 2), y, y, a=0.58, b=1.33, n_epochs=100, seed=1)
 
 
+def test_umap_knn_cross_refuses_an_out_tuple_of_the_wrong_length():
+    """The length of ``out=(knn_idx, knn_dist)`` is checked before anything else, so no device is needed."""
+    from pti_ldm_vae_amd import ops
+    for out in ((None,), (None, None, None)):
+        with pytest.raises(ValueError, match=r"umap_knn_cross: out must be \(knn_idx, knn_dist\)"):
+            ops.umap_knn_cross(torch.rand(5, 8), 3, out=out)
+
+
 # ---- API and CLI -------------------------------------------------------------------------------------------------------------
 ARGV = ["--vae-weights", "w.pth", "--config-file", "c.json", "--folder-edente", "e"]
 
