@@ -341,6 +341,30 @@ int pti_ar_vae_loss(const float* mu_nchw, int b, int l, int hw, const float* att
 int pti_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                   float beta2, float eps, int step, float grad_scale, pti_stream_t s);
 
+/* ---- guarded optimiser step: global-norm clip, skip on a non-finite gradient, EMA of the weights ----
+ * Three launches per step on the caller's stream, no atomics, no host read-back: the decision stays in `ctl`, a
+ * persistent control record of PTI_GRAD_GUARD_COLUMNS doubles per optimiser (zeroed once by its owner):
+ *   0 applied_steps  1 skipped_steps  2 sumsq of the last step  3 norm = grad_scale * sqrt(sumsq), before clipping
+ *   4 coef           5 skip (0 | 1)   6 bias1 = 1 - beta1^t     7 bias2_sqrt = sqrt(1 - beta2^t), t = applied_steps + 1
+ *   8 the EMA decay in effect         9 grad_scale * coef, the factor the step applies to g
+ * (columns 0..7, 64 bytes, are what a host reads back; 8 and 9 pass values to pti_adam_step_guarded.)
+ * pti_grad_guard_partials(n): workgroups of the norm pass = {sumsq, non-finite count} pairs in `partials` -- a function
+ *   of n only, at most PTI_GRAD_GUARD_PARTIALS_CAP, 0 for n < 1; pure host arithmetic.
+ * pti_grad_guard: g fp32 [n] (4-byte alignment suffices), partials: 2 * pti_grad_guard_partials(n) doubles of scratch, 16-byte aligned.
+ *   fp64 sum of squares in a fixed order; bad = a non-finite element or a non-finite norm; skip = bad and skip_nonfinite;
+ *   coef = min(1, max_norm / (norm + 1e-6)) when max_norm > 0 and not bad, else 1 (max_norm 0: no clipping).  A skipped
+ *   step advances skipped_steps only; any other advances applied_steps and renews columns 6..8, the decay being
+ *   min(ema_decay, (1 + t) / (10 + t)) (ema_decay 0: no EMA).
+ * pti_adam_step_guarded: pti_adam_step's arithmetic on g * ctl[9] with the bias corrections of ctl[6..7]; with `ema`
+ *   (NULL: none) also ema += (1 - ctl[8]) * (p_new - ema) in the same pass.  With ctl[5] set nothing is written.      */
+#define PTI_GRAD_GUARD_PARTIALS_CAP 1024
+#define PTI_GRAD_GUARD_COLUMNS 10
+int pti_grad_guard_partials(int64_t n);
+int pti_grad_guard(const float* g, int64_t n, double grad_scale, double max_norm, int skip_nonfinite, float beta1,
+                   float beta2, double ema_decay, double* partials, double* ctl, pti_stream_t s);
+int pti_adam_step_guarded(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1,
+                          float beta2, float eps, const double* ctl, pti_stream_t s);
+
 /* ---- layout casts at the model boundary ------------------------------------------------------ */
 int pti_cast_nchw_f32_to_nhwc_bf16(const float* x, void* y, int n, int c, int hw, pti_stream_t s);
 int pti_cast_nhwc_bf16_to_nchw_f32(const void* x, float* y, int n, int c, int hw, pti_stream_t s);

@@ -63,6 +63,12 @@ MASK_COMPARE_COLUMNS = ("n_gt", "n_pred", "components_gt", "components_pred", "k
 # the int64 columns of pti_mask_moments' moments and the int32 columns of pti_align_bottom's info ("pair registration")
 MASK_MOMENTS_COLUMNS = ("m00", "m10", "m01", "m20", "m11", "m02", "A", "B", "C", "status")
 ALIGN_BOTTOM_COLUMNS = ("centre_gt", "centre_pred", "count_gt", "count_pred", "shift", "status")
+# the fp64 columns of the guarded optimiser step's control record ("guarded optimiser step"): PTI_GRAD_GUARD_COLUMNS;
+# a host reads the first GRAD_GUARD_HOST_COLUMNS (64 bytes), the last two only pass values between the kernels
+GRAD_GUARD_COLUMNS = ("applied_steps", "skipped_steps", "sumsq", "norm", "coef", "skip", "bias1", "bias2_sqrt",
+                      "ema_decay", "grad_mul")
+GRAD_GUARD_HOST_COLUMNS = 8
+GRAD_GUARD_PARTIALS_CAP = 1024   # PTI_GRAD_GUARD_PARTIALS_CAP
 
 
 class DirectRepackEntry(C.Structure):
@@ -160,6 +166,9 @@ SIGNATURES = {
     "pti_lpips_tap_nhwc_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "pti_lpips_tap_nhwc_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "pti_adam_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _F, _P]),
+    "pti_grad_guard_partials": (_I, [_I64]),
+    "pti_grad_guard": (_I, [_P, _I64, _D, _D, _I, _F, _F, _D, _P, _P, _P]),
+    "pti_adam_step_guarded": (_I, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _P]),
     "pti_preprocess_batch": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "pti_cast_nchw_f32_to_nhwc_bf16": (_I, [_P, _P, _I, _I, _I, _P]),
     "pti_cast_nhwc_bf16_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _P]),

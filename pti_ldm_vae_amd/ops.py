@@ -664,6 +664,65 @@ def adam_step(p, g, m, v, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=1, grad_
                                   grad_scale, _stream()), "pti_adam_step")
 
 
+# ---- guarded optimiser step (csrc/optim_guard.hip; include/pti_vae.h "guarded optimiser step") ---------------------------
+GRAD_GUARD_COLUMNS = L.GRAD_GUARD_COLUMNS                    # the fp64 columns of the control record, in order
+GRAD_GUARD_HOST_COLUMNS = L.GRAD_GUARD_HOST_COLUMNS          # the first 64 bytes: what a host reads back
+GRAD_GUARD_PARTIALS_CAP = L.GRAD_GUARD_PARTIALS_CAP          # PTI_GRAD_GUARD_PARTIALS_CAP
+
+
+def grad_guard_ctl(device):
+    """A zeroed control record for one optimiser: fp64 [len(GRAD_GUARD_COLUMNS)]."""
+    return torch.zeros(len(GRAD_GUARD_COLUMNS), dtype=torch.float64, device=device)
+
+
+def _chk_ctl(who, ctl, device):
+    if not isinstance(ctl, torch.Tensor):
+        raise ValueError(f"{who}: ctl: expected a CUDA(HIP) tensor")
+    _chk(ctl, torch.float64, "ctl", 1)
+    if ctl.numel() != len(GRAD_GUARD_COLUMNS) or ctl.device != device:
+        raise ValueError(f"{who}: ctl must be fp64 [{len(GRAD_GUARD_COLUMNS)}] on {device}")
+
+
+def grad_guard(g, *, ctl, grad_scale=1.0, max_norm=None, skip_nonfinite=False, betas=(0.9, 0.999), ema_decay=None):
+    """Norm pass + decision of a guarded step (``pti_grad_guard``, two launches on the current stream, no host sync):
+    ``ctl`` (``grad_guard_ctl``) then holds the fp64 sum of squares of ``g`` (flat fp32, 4-byte alignment suffices), the
+    norm ``grad_scale * sqrt(sumsq)``, the clip coefficient for ``max_norm`` (None: no clipping), whether the step is
+    skipped (a non-finite gradient with ``skip_nonfinite``), and the step counters, bias corrections and EMA decay
+    (``ema_decay`` None: no EMA) that ``adam_step_guarded`` reads.  -> the partials buffer (cached per stream and size)."""
+    _chk(g, F32, "g", 1)
+    _chk_ctl("grad_guard", ctl, g.device)
+    n = g.numel()
+    nparts = L.lib().pti_grad_guard_partials(n)
+    stream = _stream()
+    ws, _ = _scratch_bytes("grad_guard", "grad_guard", (n,), 16 * nparts, (n,), g.device, stream)
+    prof = KERNEL_PROFILE
+    rec = None if prof is None else _prof_begin(prof)
+    L.check(L.lib().pti_grad_guard(_ptr(g), n, float(grad_scale), 0.0 if max_norm is None else float(max_norm),
+                                   int(bool(skip_nonfinite)), betas[0], betas[1], 0.0 if ema_decay is None else float(ema_decay),
+                                   _ptr(ws), _ptr(ctl), stream), "pti_grad_guard")
+    if rec is not None:     # both launches; the name is the decision kernel's
+        _prof_end(rec, 2.0 * n, 4.0 * n + 32.0 * nparts, ("grad_guard", n))
+    return ws
+
+
+def adam_step_guarded(p, g, m, v, *, ctl, lr, betas=(0.9, 0.999), eps=1e-8, ema=None):
+    """``adam_step`` as ``grad_guard`` left it in ``ctl``: nothing on a skipped step, else Adam on ``g * (grad_scale * coef)``
+    at ``t = applied_steps``, and with ``ema`` (an arena like ``p``) ``ema += (1 - decay) * (p_new - ema)`` in the same pass
+    (``pti_adam_step_guarded``)."""
+    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")) + (((ema, "ema"),) if ema is not None else ()):
+        _chk(t, F32, nm)
+        if t.numel() != p.numel():
+            raise ValueError("adam_step_guarded: size mismatch")
+    _chk_ctl("adam_step_guarded", ctl, p.device)
+    n = p.numel()
+    prof = KERNEL_PROFILE
+    rec = None if prof is None else _prof_begin(prof)
+    L.check(L.lib().pti_adam_step_guarded(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), n, lr, betas[0], betas[1], eps,
+                                          _ptr(ctl), _stream()), "pti_adam_step_guarded")
+    if rec is not None:
+        _prof_end(rec, 12.0 * n, (28.0 if ema is None else 36.0) * n, ("adam_step_guarded", n, ema is not None))
+
+
 def cast_nchw_f32_to_nhwc_bf16(x, y):
     n, c = x.shape[0], x.shape[1]
     _chk(x, F32, "x")

@@ -32,7 +32,12 @@ What is different, on purpose:
     every 5th epoch, train_vae.py:536-549,610-618) are written as the reference writes them, without a host sync per
     validation step; the validation triplet it logs to W&B every 20 epochs (:620-626) is written as
     ``triplets/val_epochEEE_stepSSS.png`` from one ``pti_display_planes`` launch (``utils/validation_samples.py``;
-    ``--val-samples-start / --val-samples-every / --val-triplet-every``).  The train-step triplet is not written.
+    ``--val-samples-start / --val-samples-every / --val-triplet-every``).  The train-step triplet is not written;
+  * not in the reference: ``grad_clip_norm`` / ``skip_nonfinite_steps`` / ``ema_decay`` under ``autoencoder_train`` switch on
+    the guarded optimiser step (``optim.py``; off when absent): global-norm clipping, no update on a non-finite
+    gradient, an EMA of the weights -- decided on the device, logged as ``train/grad_norm`` / ``train/grad_clip_coef`` /
+    ``train/skipped_steps``, the EMA written as ``autoencoder_ema_last.pt`` / ``autoencoder_ema_epoch{E}.pth`` and as
+    ``ema_state_dict`` in the checkpoint.
 """
 from __future__ import annotations
 
@@ -47,7 +52,7 @@ import torch
 
 from .models import PatchDiscriminator, PerceptualLoss, VAEModel, compute_total_loss
 from .trainer import ARSettings, VAETrainer, prepare_batch
-from .utils import read_config, resolve_ar_settings
+from .utils import read_config, resolve_ar_settings, resolve_guard_settings
 from .utils.distributed import setup_ddp
 from .utils.validation_samples import ValidationSampleWriter
 
@@ -177,6 +182,10 @@ def save_checkpoints(args, model, opt, epoch, val_loss, best_val_loss, best_epoc
         return best_val_loss, best_epoch_saved
     sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     torch.save(sd, os.path.join(args.model_dir, "autoencoder_last.pt"))
+    esd = None      # the EMA of the weights (autoencoder_train.ema_decay): a plain state dict beside every weights file
+    if getattr(opt, "ema_decay", None) is not None:
+        esd = {k: v.detach().cpu() for k, v in opt.ema_state_dict().items()}
+        torch.save(esd, os.path.join(args.model_dir, "autoencoder_ema_last.pt"))
     dsd = None
     if disc is not None:
         dsd = {k: v.detach().cpu() for k, v in disc.state_dict().items()}
@@ -184,11 +193,14 @@ def save_checkpoints(args, model, opt, epoch, val_loss, best_val_loss, best_epoc
     if val_loss >= best_val_loss:
         return best_val_loss, best_epoch_saved
     if best_epoch_saved is not None:
-        for f in (f"checkpoint_epoch{best_epoch_saved}.pth", f"autoencoder_epoch{best_epoch_saved}.pth"):
+        for f in (f"checkpoint_epoch{best_epoch_saved}.pth", f"autoencoder_epoch{best_epoch_saved}.pth",
+                  f"autoencoder_ema_epoch{best_epoch_saved}.pth"):
             f = os.path.join(args.model_dir, f)
             if os.path.exists(f):
                 os.remove(f)
     torch.save(sd, os.path.join(args.model_dir, f"autoencoder_epoch{epoch}.pth"))
+    if esd is not None:
+        torch.save(esd, os.path.join(args.model_dir, f"autoencoder_ema_epoch{epoch}.pth"))
     if dsd is not None:
         torch.save(dsd, os.path.join(args.model_dir, f"discriminator_epoch{epoch}.pth"))
 
@@ -197,10 +209,13 @@ def save_checkpoints(args, model, opt, epoch, val_loss, best_val_loss, best_epoc
             st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].cpu(), st["exp_avg_sq"].cpu()
         return osd
     osd = host(opt.state_dict())
-    torch.save({"epoch": epoch, "autoencoder_state_dict": sd, "discriminator_state_dict": dsd,
-                "optimizer_g_state_dict": osd, "optimizer_d_state_dict": host(opt_d.state_dict()) if opt_d is not None else None,
-                "best_val_loss": val_loss,
-                "total_step": total_step}, os.path.join(args.model_dir, f"checkpoint_epoch{epoch}.pth"))
+    ck = {"epoch": epoch, "autoencoder_state_dict": sd, "discriminator_state_dict": dsd,
+          "optimizer_g_state_dict": osd, "optimizer_d_state_dict": host(opt_d.state_dict()) if opt_d is not None else None,
+          "best_val_loss": val_loss,
+          "total_step": total_step}
+    if esd is not None:
+        ck["ema_state_dict"] = esd
+    torch.save(ck, os.path.join(args.model_dir, f"checkpoint_epoch{epoch}.pth"))
     print(f"Best models saved for epoch {epoch}")
     return val_loss, epoch
 
@@ -216,6 +231,12 @@ def load_checkpoint(args, model, opt, device, disc=None, opt_d=None):
     ck = torch.load(path, map_location=device, weights_only=True)
     model.load_state_dict(ck["autoencoder_state_dict"])
     opt.load_state_dict(ck["optimizer_g_state_dict"])
+    if getattr(opt, "ema_decay", None) is not None:
+        if ck.get("ema_state_dict") is not None:
+            opt.load_ema_state_dict(ck["ema_state_dict"])
+        else:
+            opt.load_ema_state_dict(ck["autoencoder_state_dict"])
+            print("[INFO] The checkpoint holds no ema_state_dict: the EMA starts from the loaded weights")
     if disc is not None and ck.get("discriminator_state_dict") is not None:     # train_vae.py:320-331
         disc.load_state_dict(ck["discriminator_state_dict"])
         if opt_d is not None and ck.get("optimizer_d_state_dict") is not None:
@@ -232,6 +253,8 @@ def main(argv=None):
     args = load_config(args)
     tr = args.autoencoder_train
     ar_enabled, ar_gamma, _, _ = resolve_ar_settings(tr, getattr(args, "regularized_attributes", {}))
+    clip_norm, skip_nonfinite, ema_decay = resolve_guard_settings(tr)
+    guard_on = clip_norm is not None or skip_nonfinite or ema_decay is not None
     adv_enabled = bool(tr.get("adv_enabled", True))
     unavailable = []
     perceptual_weight = float(tr.get("perceptual_weight", 0.0))
@@ -268,7 +291,8 @@ def main(argv=None):
     adv_weight = float(tr.get("adv_weight", 0.0))
     trainer = VAETrainer(model, lr=tr["lr"], world_size=world, process_group=pg, recon_loss=tr.get("recon_loss", "l1"),
                          kl_weight=tr["kl_weight"], rank_eps_offset=rank, ar=ar, discriminator=disc, adv_weight=adv_weight,
-                         perceptual=perceptual, perceptual_weight=perceptual_weight)
+                         perceptual=perceptual, perceptual_weight=perceptual_weight, clip_norm=clip_norm,
+                         skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
     opt_d = trainer.opt_d if disc is not None else None
     start_epoch, best_val, total_step, best_epoch_saved = load_checkpoint(args, model, trainer.opt, device, disc, opt_d)
     model.autoencoder.mark_weights_dirty()
@@ -328,6 +352,10 @@ def main(argv=None):
                     rec["train/ar_loss_total"] = out["ar"].item()
                     for name, la, cnt, dl in zip(ar.names, out["ar_per_attr"].tolist(), out["ar_pairs"].tolist(), ar.deltas):
                         rec[f"train/ar_loss_{name}"], rec[f"train/ar_pairs_{name}"], rec[f"train/ar_delta_{name}"] = la, cnt, dl
+                if guard_on:         # the VAE optimiser's guard at this step (the .item() calls above have synchronised)
+                    gs = trainer.opt.guard_stats()
+                    rec["train/grad_norm"], rec["train/grad_clip_coef"] = gs["grad_norm"], gs["clip_coef"]
+                    rec["train/skipped_steps"] = gs["skipped_steps"]
                 log.write(json.dumps(rec) + "\n")
                 log.flush()
         if epoch % val_interval == 0:

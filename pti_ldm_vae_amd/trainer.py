@@ -111,13 +111,16 @@ class VAETrainer:
                  kl_weight: float = 1e-3, kl_input_is_logvar: bool = True, bucket_bytes: int = 4 << 20,
                  rank_eps_offset: int = 0, ar: ARSettings | None = None, discriminator=None, adv_weight: float = 0.0,
                  lr_d: float | None = None, adv_no_activation_leastsq: bool = False, perceptual=None,
-                 perceptual_weight: float = 0.0):
+                 perceptual_weight: float = 0.0, clip_norm: float | None = None, skip_nonfinite: bool = False,
+                 ema_decay: float | None = None):
         self.model = model
         self.net = net = model.autoencoder
         self.eng = net.engine()
         self.world = world_size
-        # reference: lr scaled by world size (train_vae.py:301); gradients averaged like DDP
-        self.opt = FlatAdam(net, lr * world_size)
+        # reference: lr scaled by world size (train_vae.py:301); gradients averaged like DDP.  The guarded step
+        # (clip_norm / skip_nonfinite / ema_decay, optim.py) decides on the device from the all-reduced arena: every rank
+        # holds the same gradients, so every rank takes the same decision without a further exchange.
+        self.opt = FlatAdam(net, lr * world_size, clip_norm=clip_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
         self.l2 = recon_loss == "l2"
         self.kl_weight = float(kl_weight)
         self.third_mode = 0 if kl_input_is_logvar else 1
@@ -152,7 +155,9 @@ class VAETrainer:
         if discriminator is not None:
             self.disc_eng = discriminator.engine()
             discriminator.attach_grads()
-            self.opt_d = FlatAdam(discriminator, (lr if lr_d is None else lr_d) * world_size)
+            # clip and skip guard the discriminator too, with a record of its own; the EMA is the VAE's only
+            self.opt_d = FlatAdam(discriminator, (lr if lr_d is None else lr_d) * world_size, clip_norm=clip_norm,
+                                  skip_nonfinite=skip_nonfinite)
             self.reducer_d = FlatGradAllReducer(discriminator.grad_arena, process_group, bucket_bytes)
             broadcast_parameters(discriminator.param_arena, process_group)
             discriminator.mark_weights_dirty()

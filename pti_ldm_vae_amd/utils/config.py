@@ -11,6 +11,7 @@ relies on (``vae_scripts/train_vae.py:100-124``, ``src/pti_ldm_vae/utils/vae_loa
 from __future__ import annotations
 
 import json
+import math
 import re
 from types import SimpleNamespace
 from typing import Any
@@ -83,3 +84,23 @@ def resolve_ar_settings(autoencoder_train: dict, regularized_attributes: dict | 
     else:
         gamma = float(raw)
     return enabled, gamma, ra.get("pairwise", "all"), ra.get("subset_pairs")
+
+
+def resolve_guard_settings(autoencoder_train: dict):
+    """The guarded optimiser step's keys (not in the reference; all off when absent) -> ``(clip_norm, skip_nonfinite,
+    ema_decay)``: ``grad_clip_norm`` a finite positive number or null, ``skip_nonfinite_steps`` a bool (``resolve_bool``'s
+    strings too), ``ema_decay`` a number in (0, 1) or null.  Anything else is a ``ValueError`` naming the key."""
+    def number(key, ok, want):
+        v = autoencoder_train.get(key)
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not ok(v):
+            raise ValueError(f"autoencoder_train.{key} must be {want} or null, got {v!r}")
+        return float(v)
+
+    clip = number("grad_clip_norm", lambda v: v > 0, "a finite positive number")
+    ema = number("ema_decay", lambda v: 0.0 < v < 1.0, "a number in (0, 1)")
+    skip = autoencoder_train.get("skip_nonfinite_steps", False)
+    if not isinstance(skip, (bool, str)) and skip is not None:
+        raise ValueError(f"autoencoder_train.skip_nonfinite_steps must be true or false, got {skip!r}")
+    return clip, resolve_bool(skip), ema
