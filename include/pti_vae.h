@@ -50,6 +50,8 @@ typedef void* pti_stream_t; /* hipStream_t */
                                Still 5: pti_mask_moments (+ its _ws_bytes) / pti_warp_cubic / pti_align_bottom appended in
                                the same way.
                                Still 5: pti_ssim_uniform (+ its _ws_bytes) / pti_mask_compare_cleaned appended in the same
+                               way.
+                               Still 5: pti_mask_compare_outputs / pti_surface_distance (+ its _ws_bytes) appended in the same
                                way. */
 
 #define PTI_OK 0
@@ -994,6 +996,52 @@ int pti_ssim_uniform(const float* x, const float* y, int n, int h, int w, double
                      int64_t ws_bytes, pti_stream_t s);
 int pti_mask_compare_cleaned(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts,
                              double* sums, float* cleaned, void* workspace, int64_t ws_bytes, pti_stream_t s);
+
+/* ---- surface distance between the two regions of a pair (Hausdorff, its percentile form, the average symmetric surface
+ *      distance, surface Dice; csrc/surface_distance.hip) ----
+ * pti_mask_compare_outputs is pti_mask_compare -- the same launch, the same counts and sums bit for bit -- with two optional
+ * outputs, either of which may be null: cleaned as for pti_mask_compare_cleaned, and masks uint8 [n][h][w] with bit 0 = G
+ * (gt != 0) and bit 1 = P (the filled largest component of the prediction): exactly the two regions the Dice is formed from.
+ * (cleaned != 0 is NOT P: a filled hole can hold zeros.)  masks is all 0 in a row whose status is 1.  No output may alias an
+ * input or the other output.
+ *
+ * pti_surface_distance: a, b uint8 [n][h][w], dense; they may be the same pointer.  A pixel p is foreground on side 0 when
+ * a[p] & a_bits and on side 1 when b[p] & b_bits (1 <= bits <= 255; masks of pti_mask_compare_outputs: a == b, bits 1 and 2).
+ *   Edge pixel: a foreground pixel with at least one of its four neighbours not foreground; pixels outside the image count as
+ *               background.  (mask ^ binary_erosion(mask) with scipy's default cross: the rule of MONAI's get_mask_edges.)
+ *   Distance:   for every edge pixel p of side s, d2(p) = min |p - q|^2 over the edge pixels q of side 1 - s: an exact
+ *               integer, at most 2 * 1023^2.
+ * counts: int32 [n][2][PTI_SURFACE_COLUMNS], per image and side the columns
+ *    0 n_fg     foreground pixels              1 n_edge   edge pixels (m)            2 max_d2   the largest d2
+ *    3 rank_lo  ((m - 1) percentile_pm) / 1000 in integer arithmetic
+ *    4 d2_lo    the rank_lo-th smallest d2, counted from 0
+ *    5 d2_hi    the next one when ((m - 1) percentile_pm) % 1000 != 0, else d2_lo
+ *    6..9 within_j  edge pixels with d2 <= tol_d2[j]; 0 for j >= n_tol           10 status  0 (1: internal inconsistency)
+ *   The percentile_pm / 1000 quantile of the distances, with linear interpolation, is
+ *   sqrt(d2_lo) + (((m - 1) percentile_pm) % 1000) / 1000 * (sqrt(d2_hi) - sqrt(d2_lo)).
+ * sums: fp64 [n][2]: the sum of sqrt(d2), correctly rounded roots, over the side's edge pixels, added in ONE order that depends
+ *   on h and w alone (lane: left to right, wave butterfly, rows in order): no floating-point atomics, bitwise reproducible.
+ * An empty side: if EITHER side of an image has no edge pixel, both its rows hold max_d2 = d2_lo = d2_hi = -1, rank_lo = 0,
+ *   within = 0 and sum 0.0; n_fg and n_edge stay true.
+ * tol_d2: HOST array of n_tol <= PTI_SURFACE_MAX_TOLERANCES int32 >= 0, read before the call returns (for a tolerance of t
+ *   pixels pass floor(t t): for an integer d2, d <= t is d2 <= floor(t^2)).  0 <= percentile_pm <= 1000.
+ * Three launches on the caller's stream, no host synchronisation: a column pass (edge flags, vertical distances), a row pass
+ * (one wave per row; an edge pixel scans at most w columns) and a select pass per (image, side).  An image's rows do not
+ * depend on n or on its place in the batch.
+ * workspace: pti_surface_distance_ws_bytes(n, h, w) bytes (12 per pixel and image, plus a few KB), 8-byte aligned, ws_bytes =
+ * its size (pure host arithmetic; 0 = unsupported shape); every word read is written earlier in the same call.  Refused before
+ * any launch: null pointers, n, h or w < 1, bits outside 1 .. 255, percentile_pm outside 0 .. 1000, n_tol outside 0 ..
+ * PTI_SURFACE_MAX_TOLERANCES, a negative tolerance, a misaligned buffer, a misaligned or short workspace (PTI_EINVAL); h or w >
+ * PTI_MASK_COMPARE_MAX_EDGE, n > 32767 (PTI_EUNSUPPORTED).                                                                */
+#define PTI_SURFACE_COLUMNS 11
+#define PTI_SURFACE_MAX_TOLERANCES 4
+int pti_mask_compare_outputs(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts,
+                             double* sums, float* cleaned_or_null, uint8_t* masks_or_null, void* workspace, int64_t ws_bytes,
+                             pti_stream_t s);
+int64_t pti_surface_distance_ws_bytes(int n, int h, int w);
+int pti_surface_distance(const uint8_t* a, int a_bits, const uint8_t* b, int b_bits, int n, int h, int w, int percentile_pm,
+                         const int32_t* tol_d2, int n_tol, int32_t* counts, double* sums, void* workspace, int64_t ws_bytes,
+                         pti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,10 @@ MASK_COMPARE_COLUMNS = ("n_gt", "n_pred", "components_gt", "components_pred", "k
 # the int64 columns of pti_mask_moments' moments and the int32 columns of pti_align_bottom's info ("pair registration")
 MASK_MOMENTS_COLUMNS = ("m00", "m10", "m01", "m20", "m11", "m02", "A", "B", "C", "status")
 ALIGN_BOTTOM_COLUMNS = ("centre_gt", "centre_pred", "count_gt", "count_pred", "shift", "status")
+# the int32 columns of pti_surface_distance's counts per (image, side) ("surface distance"): PTI_SURFACE_COLUMNS of them
+SURFACE_COLUMNS = ("n_fg", "n_edge", "max_d2", "rank_lo", "d2_lo", "d2_hi", "within_0", "within_1", "within_2", "within_3",
+                   "status")
+SURFACE_MAX_TOLERANCES = 4   # PTI_SURFACE_MAX_TOLERANCES
 # the fp64 columns of the guarded optimiser step's control record ("guarded optimiser step"): PTI_GRAD_GUARD_COLUMNS;
 # a host reads the first GRAD_GUARD_HOST_COLUMNS (64 bytes), the last two only pass values between the kernels
 GRAD_GUARD_COLUMNS = ("applied_steps", "skipped_steps", "sumsq", "norm", "coef", "skip", "bias1", "bias2_sqrt",
@@ -220,6 +224,9 @@ SIGNATURES = {
     "pti_ssim_uniform_ws_bytes": (_I64, [_I, _I, _I]),
     "pti_ssim_uniform": (_I, [_P, _P, _I, _I, _I, _D, _P, _P, _I64, _P]),
     "pti_mask_compare_cleaned": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _I64, _P]),
+    "pti_mask_compare_outputs": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I64, _P]),
+    "pti_surface_distance_ws_bytes": (_I64, [_I, _I, _I]),
+    "pti_surface_distance": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _P, _P, _P, _I64, _P]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@ of exams within 5 / 10 pixels or above 90 / 95 / 97 %.
     python -m pti_ldm_vae_amd.compare_images --results-dir inference_vae_<checkpoint>/results_tif
     python -m pti_ldm_vae_amd.compare_images --results-dir ... --straighten [--write-registered DIR]
     python -m pti_ldm_vae_amd.compare_images --results-dir ... --ssim
+    python -m pti_ldm_vae_amd.compare_images --results-dir ... --surface [--surface-tolerances 1 2] [--surface-percentile 95]
 
 ``--gt-dir`` / ``--pred-dir`` pair the ``.tif`` / ``.tiff`` files of two folders by file name (files present in one folder
 only are reported); ``--results-dir`` takes the ``[input | reconstruction]`` files ``inference_vae`` writes: the left half is
@@ -31,6 +32,16 @@ and the two doubles per image travel in the same copy back.  Each metric diction
 for a constant ground truth (data range 0) and for an image with an edge below 7 pixels; such a pair keeps its other metrics
 (the reference drops it).  This is NOT ``evaluate_vae``'s SSIM (Gaussian window, zero padding, fixed range, raw reconstruction).
 Without ``--ssim`` every output is what it was.
+
+``--surface`` adds how far the outlines are apart, in pixels: ``"Hausdorff Distance"``, ``"Hausdorff Distance 95"`` (the
+``--surface-percentile`` of the directed distances, the larger side), ``"Average Surface Distance"`` (the pooled symmetric mean)
+and one ``"Surface Dice @ t px"`` per ``--surface-tolerances`` value (edge pixels within ``t``, pixel counts, not surfel
+lengths), between exactly the two regions the Dice is formed from: the ground-truth mask and the prediction's filled largest
+component (with ``--straighten`` those of the registered pair).  The ``mask_compare`` launch writes both regions as bits,
+``ops.surface_distance`` (csrc/surface_distance.hip, an exact Euclidean distance transform, three launches) follows on the same
+stream and its 13 doubles per image travel in the same copy back.  The keys come after the existing ones, an image gains a
+``"surface"`` block (both directed maxima, percentile values, means and edge counts) and all values are ``None`` when a side has
+no outline.  Without ``--surface`` every output is what it was.
 
 ``--straighten`` registers every pair before it is measured, as the reference does: both sides are turned until the object's
 major axis is vertical (orientation from the second moments of the filled largest component, 4 x 4 cubic rotation about
@@ -71,7 +82,24 @@ def parse_args(argv=None) -> argparse.Namespace:
                         help="with --straighten: write [rotated ground truth | aligned prediction] TIFs of the compared pairs here")
     parser.add_argument("--ssim", action="store_true",
                         help="also report skimage's uniform-window SSIM of the ground truth and the cleaned prediction")
+    parser.add_argument("--surface", action="store_true",
+                        help="also report Hausdorff, its percentile form, the average surface distance and surface Dice of the two "
+                             "masks' outlines, in pixels; a batch is cut so that the distance kernel's scratch stays under 1 GiB")
+    parser.add_argument("--surface-tolerances", type=float, nargs="+", default=None, metavar="T",
+                        help="with --surface: up to 4 surface Dice tolerances in pixels (default: 1 2)")
+    parser.add_argument("--surface-percentile", type=float, default=None,
+                        help="with --surface: the percentile of the robust Hausdorff distance, a multiple of 0.1 (default: 95)")
     args = parser.parse_args(argv)
+    if not args.surface and (args.surface_tolerances is not None or args.surface_percentile is not None):
+        parser.error("--surface-tolerances and --surface-percentile need --surface")
+    if args.surface:
+        args.surface_tolerances = [1.0, 2.0] if args.surface_tolerances is None else args.surface_tolerances
+        args.surface_percentile = 95.0 if args.surface_percentile is None else args.surface_percentile
+        if len(args.surface_tolerances) > 4 or any(not t >= 0.0 for t in args.surface_tolerances):
+            parser.error(f"--surface-tolerances takes at most 4 values >= 0, got {args.surface_tolerances}")
+        pm = round(args.surface_percentile * 10.0)
+        if not 0 <= pm <= 1000 or abs(args.surface_percentile * 10.0 - pm) > 1e-9:
+            parser.error(f"--surface-percentile must be a multiple of 0.1 in 0 .. 100, got {args.surface_percentile}")
     if args.write_registered is not None and not args.straighten:
         parser.error("--write-registered needs --straighten")
     pair_mode = args.gt_dir is not None or args.pred_dir is not None
@@ -163,23 +191,32 @@ def registration_skip(moments, align):
     return NO_BOTTOM + {1: "ground truth", 2: "prediction", 3: "ground truth and the prediction"}[bad] if bad else None
 
 
-def _measure(gt, pred, threshold, counts, sums, ssim_out):
+SURFACE_SCRATCH_CAP = 1 << 30   # bytes of ops.surface_distance's scratch a --surface batch may ask for
+
+
+def _measure(gt, pred, threshold, counts, sums, ssim_out, surface=None):
     """``ops.mask_compare`` of a pair of device batches; with ``ssim_out`` (the ``[n, 2]`` tail of the batch's buffer) the launch
     also writes the cleaned prediction and ``ops.ssim_uniform`` of (gt, cleaned) follows on the same stream.  A batch with an
-    edge below 7 pixels has no window: its rows are zeroed instead (range 0: ``pair_metrics`` reports ``None``)."""
+    edge below 7 pixels has no window: its rows are zeroed instead (range 0: ``pair_metrics`` reports ``None``).
+
+    ``surface = (counts view, sums view, tolerances, percentile)``: the launch also writes the two regions as bits and
+    ``ops.surface_distance`` of them follows on the same stream, into those views of the batch's buffer."""
     from . import ops
+    more = {} if surface is None else {"masks": True}
     if ssim_out is None:
-        ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums))
+        got = ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums), **more)
     elif min(gt.shape[-2:]) < ops.SSIM_UNIFORM_MIN_EDGE:
-        ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums))
+        got = ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums), **more)
         ssim_out.zero_()
     else:
-        cleaned = ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums), cleaned=True)[2]
-        ops.ssim_uniform(gt, cleaned, out=ssim_out)
+        got = ops.mask_compare(gt, pred, threshold=threshold, out=(counts, sums), cleaned=True, **more)
+        ops.ssim_uniform(gt, got[2], out=ssim_out)
+    if surface is not None:
+        ops.surface_distance(got[-1], percentile=surface[3], tolerances=surface[2], out=(surface[0], surface[1]))
 
 
 def compare_batch(gts: list, preds: list, threshold: float, device, straighten: bool = False, images: bool = False,
-                  ssim: bool = False):
+                  ssim: bool = False, surface=None):
     """One launch and ONE copy back for a batch of one shape -> (counts int32 ``[n, 24]``, sums float64 ``[n, 3]``) on the
     host.  Both outputs are views of one device buffer (3 doubles, then 24 int32 = 12 doubles per image).
 
@@ -189,14 +226,28 @@ def compare_batch(gts: list, preds: list, threshold: float, device, straighten: 
 
     ``ssim``: ``ops.ssim_uniform`` of the measured ground truth and the cleaned prediction after ``mask_compare`` (up to three
     more launches), and one more value is returned LAST: float64 ``[n, 2]`` = ``{ssim, data range}`` -- two more doubles per
-    image at the end of the same buffer, the same copy."""
+    image at the end of the same buffer, the same copy.
+
+    ``surface = (tolerances, percentile)``: ``ops.surface_distance`` of the measured pair's two regions after that (three more
+    launches), and one more value is returned after all others: ``(counts int32 [n, 2, 11], sums float64 [n, 2])`` -- 13 more
+    doubles per image at the very end of the same buffer, the same copy."""
     import torch
 
     from . import ops
     n = len(gts)
     gt = torch.from_numpy(np.stack(gts)).to(device)
     pred = torch.from_numpy(np.stack(preds)).to(device)
-    tail = 2 * n if ssim else 0
+    base, tail_ssim = n * (44 if straighten else 15), 2 * n if ssim else 0
+    tail = tail_ssim + (13 * n if surface is not None else 0)
+    cols = len(ops.SURFACE_COLUMNS)
+
+    def surface_views(buf):
+        at = base + tail_ssim
+        return (buf[at + 2 * n:at + 13 * n].view(torch.int32).view(n, 2, cols), buf[at:at + 2 * n].view(n, 2)) + tuple(surface)
+
+    def surface_host(host):
+        at = base + tail_ssim
+        return (host[at + 2 * n:at + 13 * n].view(np.int32).reshape(n, 2, cols).copy(), host[at:at + 2 * n].reshape(n, 2).copy())
     if straighten:
         buf = torch.empty(n * 44 + tail, dtype=torch.float64, device=device)
         parts, at = [], 0
@@ -207,7 +258,8 @@ def compare_batch(gts: list, preds: list, threshold: float, device, straighten: 
         moments, coeffs = parts[2].view(torch.int64).view(n, 2, 10), parts[3].view(n, 2, 3)
         align = parts[4].view(torch.int32).view(n, len(ops.ALIGN_BOTTOM_COLUMNS))
         rot_gt, aligned, _ = ops.register_pairs(gt, pred, threshold=threshold, out=(None, None, moments, coeffs, align))
-        _measure(rot_gt, aligned, threshold, counts, sums, buf[at:].view(n, 2) if ssim else None)
+        _measure(rot_gt, aligned, threshold, counts, sums, buf[at:at + 2 * n].view(n, 2) if ssim else None,
+                 surface_views(buf) if surface is not None else None)
         host = buf.cpu().numpy()
         cut = np.cumsum([0, 3 * n, 12 * n, 20 * n, 6 * n, 3 * n])
         reg = {"moments": host[cut[2]:cut[3]].view(np.int64).reshape(n, 2, 10).copy(), "coeffs": host[cut[3]:cut[4]].reshape(n, 2, 3).copy(),
@@ -215,14 +267,17 @@ def compare_batch(gts: list, preds: list, threshold: float, device, straighten: 
         if images:
             reg["rotated_gt"], reg["aligned_pred"] = rot_gt.cpu().numpy(), aligned.cpu().numpy()
         res = (host[cut[1]:cut[2]].view(np.int32).reshape(n, -1).copy(), host[:3 * n].reshape(n, 3).copy(), reg)
-        return res + (host[cut[5]:].reshape(n, 2).copy(),) if ssim else res
+        res = res + (host[cut[5]:cut[5] + 2 * n].reshape(n, 2).copy(),) if ssim else res
+        return res + (surface_host(host),) if surface is not None else res
     buf = torch.empty(n * 15 + tail, dtype=torch.float64, device=device)
     sums = buf[:3 * n].view(n, 3)
     counts = buf[3 * n:15 * n].view(torch.int32).view(n, len(ops.MASK_COMPARE_COLUMNS))
-    _measure(gt, pred, threshold, counts, sums, buf[15 * n:].view(n, 2) if ssim else None)
+    _measure(gt, pred, threshold, counts, sums, buf[15 * n:17 * n].view(n, 2) if ssim else None,
+             surface_views(buf) if surface is not None else None)
     host = buf.cpu().numpy()
     res = (host[3 * n:15 * n].view(np.int32).reshape(n, -1).copy(), host[:3 * n].reshape(n, 3).copy())
-    return res + (host[15 * n:].reshape(n, 2).copy(),) if ssim else res
+    res = res + (host[15 * n:17 * n].reshape(n, 2).copy(),) if ssim else res
+    return res + (surface_host(host),) if surface is not None else res
 
 
 def run(args, device) -> dict:
@@ -238,18 +293,30 @@ def run(args, device) -> dict:
     results, buckets = {}, {}
     straighten = getattr(args, "straighten", False)
     with_ssim = getattr(args, "ssim", False)
+    surface = (tuple(args.surface_tolerances), args.surface_percentile) if getattr(args, "surface", False) else None
+    surface_pm = ops.surface_percentile_pm(WHO, surface[1]) if surface is not None else None
+
+    def batch_limit(shape):
+        """Pairs of this shape per launch: --batch-size, cut so that the distance kernel's scratch stays under the cap."""
+        if surface is None:
+            return args.batch_size
+        from . import _lib
+        return max(1, min(args.batch_size, SURFACE_SCRATCH_CAP // max(_lib.lib().pti_surface_distance_ws_bytes(1, *shape), 1)))
 
     def flush(shape):
         names, gts, preds = buckets.pop(shape)
-        reg = ssim_rows = None
-        got = compare_batch(gts, preds, args.threshold, device, straighten, straighten and args.write_registered is not None, with_ssim)
+        reg = ssim_rows = surf = None
+        got = compare_batch(gts, preds, args.threshold, device, straighten, straighten and args.write_registered is not None, with_ssim,
+                            surface)
+        if surface is not None:
+            got, surf = got[:-1], got[-1]
         if with_ssim:
             got, ssim_rows = got[:-1], got[-1]
         if straighten:
             counts, sums, reg = got
         else:
             counts, sums = got
-        for i, (name, row, s, m) in enumerate(zip(names, counts, sums, M.pair_metrics(counts, sums, *shape, ssim=ssim_rows))):
+        for i, (name, row, s, m) in enumerate(zip(names, counts, sums, M.pair_metrics(counts, sums, *shape, ssim=ssim_rows, surface=surf and surf + (surface[0], surface_pm)))):
             if reg is not None:
                 m = registration_skip(reg["moments"][i], reg["align"][i]) or m
             results[name] = m if isinstance(m, str) else {"metrics": m, "dimensions": M.dimensions(row),
@@ -257,6 +324,8 @@ def run(args, device) -> dict:
                                                           "sums": dict(zip(ops.MASK_COMPARE_SUMS, (float(v) for v in s)))}
             if with_ssim and not isinstance(m, str):
                 results[name]["sums"]["ssim_data_range"] = float(ssim_rows[i][1]) if min(shape) >= ops.SSIM_UNIFORM_MIN_EDGE else None
+            if surf is not None and not isinstance(m, str):
+                results[name]["surface"] = M.surface_block(surf[0][i], surf[1][i], surface_pm)
             if reg is not None and not isinstance(m, str):
                 results[name]["registration"] = registration_block(reg["moments"][i], reg["coeffs"][i], reg["align"][i])
                 if args.write_registered is not None:
@@ -277,7 +346,7 @@ def run(args, device) -> dict:
         bucket = buckets.setdefault(gt.shape, ([], [], []))
         for lst, v in zip(bucket, (name, gt, pred)):
             lst.append(v)
-        if len(bucket[0]) >= args.batch_size:
+        if len(bucket[0]) >= batch_limit(gt.shape):
             flush(gt.shape)
     for shape in list(buckets):
         flush(shape)
@@ -286,8 +355,9 @@ def run(args, device) -> dict:
     images = {name: results[name] for name in names if not isinstance(results[name], str)}
     skipped = [{"image": name, "reason": results[name]} for name in names if isinstance(results[name], str)]
     all_metrics = [v["metrics"] for v in images.values()]
-    # (a run without --ssim writes the file it wrote before the flag existed: the key appears only when it is set)
-    return {"arguments": {k: (str(v) if isinstance(v, Path) else v) for k, v in sorted(vars(args).items()) if k != "ssim" or v},
+    # (a run without --ssim or --surface writes the file it wrote before the flag existed: the keys appear only when it is set)
+    hidden = (() if with_ssim else ("ssim",)) + (() if surface is not None else ("surface", "surface_tolerances", "surface_percentile"))
+    return {"arguments": {k: (str(v) if isinstance(v, Path) else v) for k, v in sorted(vars(args).items()) if k not in hidden},
             "images_processed": len(images), "images": images, "aggregates": M.aggregate(all_metrics),
             "thresholds": [{"name": n_, "count": c, "percentage": p} for n_, c, p in M.threshold_counts(all_metrics)],
             "skipped": skipped, "unpaired": unpaired}

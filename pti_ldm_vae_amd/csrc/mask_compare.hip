@@ -38,6 +38,7 @@ struct McArgs {
   int* counts;      // [n][MC_COLS]
   double* sums;     // [n][3]
   float* cleaned;   // [n][h][w] or null: pred inside P, 0 elsewhere (pti_mask_compare_cleaned)
+  unsigned char* masks;   // [n][h][w] or null: bit 0 = G, bit 1 = P (pti_mask_compare_outputs)
   long long ws_ints_per_image;
   int h, w;
   float thr;
@@ -291,13 +292,17 @@ __global__ __launch_bounds__(MC_THREADS) void mask_compare_kernel(McArgs a) {
       if (P && x >= rbox[0] && x < rbox[0] + rbox[2]) { rw0 += y == rr0; rw1 += y == rr1; rw2 += y == rr2; }
       const float rp = P ? r : 0.0f;
       if (a.cleaned) a.cleaned[(size_t)img * npix + p] = rp;
+      if (a.masks) a.masks[(size_t)img * npix + p] = (unsigned char)((G ? 1 : 0) | (P ? 2 : 0));
       const double d = (double)g - (double)rp;
       sq += d * d;
       mg = g > mg ? g : mg;
       mp = rp > mp ? rp : mp;
     }
-  } else if (a.cleaned) {   // a step budget ran out: the status column says so, the image is all background
-    for (int p = tid; p < npix; p += MC_THREADS) a.cleaned[(size_t)img * npix + p] = 0.0f;
+  } else {   // a step budget ran out: the status column says so, the image is all background
+    if (a.cleaned)
+      for (int p = tid; p < npix; p += MC_THREADS) a.cleaned[(size_t)img * npix + p] = 0.0f;
+    if (a.masks)
+      for (int p = tid; p < npix; p += MC_THREADS) a.masks[(size_t)img * npix + p] = 0;
   }
   np = wave_sum(np); inter = wave_sum(inter);
   gw0 = wave_sum(gw0); gw1 = wave_sum(gw1); gw2 = wave_sum(gw2);
@@ -349,7 +354,7 @@ extern "C" int64_t pti_mask_compare_ws_bytes(int n, int h, int w) {
 
 namespace {
 int mc_launch(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts, double* sums,
-              float* cleaned, void* workspace, int64_t ws_bytes, pti_stream_t s) {
+              float* cleaned, uint8_t* masks, void* workspace, int64_t ws_bytes, pti_stream_t s) {
   if (!gt || !pred || !counts || !sums || !workspace) PTI_FAIL(PTI_EINVAL, "mask_compare: null pointer");
   if (n < 1 || h < 1 || w < 1) PTI_FAIL(PTI_EINVAL, "mask_compare: bad shape n=%d h=%d w=%d (all >= 1)", n, h, w);
   if (h > MC_MAX_EDGE || w > MC_MAX_EDGE)
@@ -361,7 +366,7 @@ int mc_launch(const float* gt, const float* pred, int n, int h, int w, float thr
   if (ws_bytes < pti_mask_compare_ws_bytes(n, h, w))
     PTI_FAIL(PTI_EINVAL, "mask_compare: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
              (long long)pti_mask_compare_ws_bytes(n, h, w));
-  McArgs a{gt, pred, (int*)workspace, counts, sums, cleaned, mc_ws_ints(h, w), h, w, threshold};
+  McArgs a{gt, pred, (int*)workspace, counts, sums, cleaned, masks, mc_ws_ints(h, w), h, w, threshold};
   PTI_LAUNCH(mask_compare_kernel, dim3((unsigned)n), dim3(MC_THREADS), 0, (hipStream_t)s, a);
   PTI_CHECK_LAUNCH("mask_compare");
   return PTI_OK;
@@ -370,7 +375,7 @@ int mc_launch(const float* gt, const float* pred, int n, int h, int w, float thr
 
 extern "C" int pti_mask_compare(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts,
                                 double* sums, void* workspace, int64_t ws_bytes, pti_stream_t s) {
-  return mc_launch(gt, pred, n, h, w, threshold, counts, sums, nullptr, workspace, ws_bytes, s);
+  return mc_launch(gt, pred, n, h, w, threshold, counts, sums, nullptr, nullptr, workspace, ws_bytes, s);
 }
 
 // The same launch, and the same counts and sums bit for bit, with the cleaned prediction c = pred inside P, else 0 written out:
@@ -380,7 +385,22 @@ extern "C" int pti_mask_compare_cleaned(const float* gt, const float* pred, int 
   if (!cleaned) PTI_FAIL(PTI_EINVAL, "mask_compare_cleaned: null pointer");
   if ((uintptr_t)cleaned & 3) PTI_FAIL(PTI_EINVAL, "mask_compare_cleaned: misaligned buffer");
   if (cleaned == gt || cleaned == pred) PTI_FAIL(PTI_EINVAL, "mask_compare_cleaned: the output must not alias an input");
-  return mc_launch(gt, pred, n, h, w, threshold, counts, sums, cleaned, workspace, ws_bytes, s);
+  return mc_launch(gt, pred, n, h, w, threshold, counts, sums, cleaned, nullptr, workspace, ws_bytes, s);
+}
+
+// The same launch again with either optional output, both or none: cleaned as above, and masks uint8 [n][h][w] with bit 0 = G
+// (gt != 0) and bit 1 = P (the filled largest component) -- the two regions the Dice is formed from, for the surface distances
+// (csrc/surface_distance.hip).  cleaned != 0 is not P: a filled hole can hold zeros.
+extern "C" int pti_mask_compare_outputs(const float* gt, const float* pred, int n, int h, int w, float threshold, int32_t* counts,
+                                        double* sums, float* cleaned_or_null, uint8_t* masks_or_null, void* workspace,
+                                        int64_t ws_bytes, pti_stream_t s) {
+  if ((uintptr_t)cleaned_or_null & 3) PTI_FAIL(PTI_EINVAL, "mask_compare_outputs: misaligned buffer");
+  if (cleaned_or_null && (cleaned_or_null == gt || cleaned_or_null == pred))
+    PTI_FAIL(PTI_EINVAL, "mask_compare_outputs: an output must not alias an input");
+  if (masks_or_null && ((const void*)masks_or_null == (const void*)gt || (const void*)masks_or_null == (const void*)pred ||
+                        (const void*)masks_or_null == (const void*)cleaned_or_null))
+    PTI_FAIL(PTI_EINVAL, "mask_compare_outputs: an output must not alias an input or the other output");
+  return mc_launch(gt, pred, n, h, w, threshold, counts, sums, cleaned_or_null, masks_or_null, workspace, ws_bytes, s);
 }
 
 // ---- pair registration (include/pti_vae.h "pair registration"): what the reference does to a pair BEFORE it

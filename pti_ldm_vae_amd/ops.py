@@ -7,6 +7,7 @@ Shapes are checked HERE, before any pointer reaches a kernel.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from collections import namedtuple
 
@@ -1339,9 +1340,14 @@ def _image_pair(who, names, a, b, *, min_edge=1, max_edge=MASK_COMPARE_MAX_EDGE,
     return a, b, n, h, w
 
 
-def mask_compare(gt, pred, *, threshold=0.2, out=None, cleaned=None):
+def mask_compare(gt, pred, *, threshold=0.2, out=None, cleaned=None, masks=None):
     """Foreground masks, largest component, hole fill and the shape numbers of a batch of image pairs in one launch
     (``pti_mask_compare``) -> ``(counts, sums)`` device tensors.
+
+    ``masks``: ``None``, or ``True`` / a contiguous uint8 ``[n, h, w]`` device tensor: the same launch
+    (``pti_mask_compare_outputs``) also writes the two regions the Dice is formed from, bit 0 = ``gt != 0``, bit 1 = the
+    prediction's filled largest component (``cleaned != 0`` is not that: a filled hole can hold zeros) -- the input of
+    ``surface_distance`` -- and it is appended to the return value; ``counts``, ``sums`` and ``cleaned`` are the same bits either way.
 
     ``cleaned``: ``None``, or ``True`` / a contiguous fp32 ``[n, h, w]`` device tensor (not ``gt`` or ``pred``): the same launch
     (``pti_mask_compare_cleaned``) also writes the prediction inside its cleaned mask and 0 elsewhere -- the image the MSE is
@@ -1365,7 +1371,19 @@ def mask_compare(gt, pred, *, threshold=0.2, out=None, cleaned=None):
     stream = _stream()
     ws, ws_bytes = _scratch_bytes(who, "mask_compare", (n, h, w), L.lib().pti_mask_compare_ws_bytes(n, h, w), tuple(gt.shape),
                                   gt.device, stream)
-    if cleaned is None or cleaned is False:
+    no_cleaned = cleaned is None or cleaned is False
+    if masks is not None and masks is not False:
+        masks = _out(None if masks is True else masks, (n, h, w), torch.uint8, gt.device, f"{who}: masks")
+        if not no_cleaned:
+            cleaned = _out(None if cleaned is True else cleaned, (n, h, w), F32, gt.device, f"{who}: cleaned")
+        taken = (gt.data_ptr(), pred.data_ptr()) + (() if no_cleaned else (cleaned.data_ptr(),))
+        if masks.data_ptr() in taken or (not no_cleaned and cleaned.data_ptr() in taken[:2]):
+            raise ValueError(f"{who}: cleaned and masks must not be gt, pred or each other")
+        L.check(L.lib().pti_mask_compare_outputs(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(counts), _ptr(sums),
+                                                 None if no_cleaned else _ptr(cleaned), _ptr(masks), _ptr(ws), ws_bytes, stream),
+                "pti_mask_compare_outputs")
+        return (counts, sums, masks) if no_cleaned else (counts, sums, cleaned, masks)
+    if no_cleaned:
         L.check(L.lib().pti_mask_compare(_ptr(gt), _ptr(pred), n, h, w, threshold, _ptr(counts), _ptr(sums), _ptr(ws),
                                          ws_bytes, stream), "pti_mask_compare")
         return counts, sums
@@ -1405,6 +1423,71 @@ def ssim_uniform(gt, pred, *, data_range=None, out=None):
     L.check(L.lib().pti_ssim_uniform(_ptr(gt), _ptr(pred), n, h, w, -1.0 if data_range is None else data_range, _ptr(out),
                                      _ptr(ws), ws_bytes, stream), "pti_ssim_uniform")
     return out
+
+
+# ---- surface distance between two regions (csrc/surface_distance.hip; include/pti_vae.h "surface distance") --------------
+SURFACE_COLUMNS = L.SURFACE_COLUMNS                       # the int32 columns per (image, side), in order
+SURFACE_MAX_TOLERANCES = L.SURFACE_MAX_TOLERANCES
+
+
+def surface_percentile_pm(who, percentile) -> int:
+    """A percentile in per-mille; it must be a multiple of 0.1 in 0 .. 100."""
+    pm = round(float(percentile) * 10.0)
+    if not (0 <= pm <= 1000) or abs(float(percentile) * 10.0 - pm) > 1e-9:
+        raise ValueError(f"{who}: percentile must be a multiple of 0.1 in 0 .. 100, got {percentile}")
+    return int(pm)
+
+
+def surface_tolerances_d2(who, tolerances) -> list:
+    """Tolerances in pixels -> ``floor(t * t)`` each (capped at int32): for an integer ``d2``, ``d <= t`` is ``d2 <= floor(t^2)``."""
+    tolerances = [float(t) for t in tolerances]
+    if len(tolerances) > SURFACE_MAX_TOLERANCES or any(not t >= 0.0 for t in tolerances):
+        raise ValueError(f"{who}: at most {SURFACE_MAX_TOLERANCES} tolerances, each >= 0, got {tolerances}")
+    return [int(math.floor(min(t * t, 2.0 ** 31 - 1))) for t in tolerances]
+
+
+def surface_distance(masks, other=None, *, percentile=95.0, tolerances=(), out=None):
+    """Distances between the outlines of two binary regions per image (``pti_surface_distance``) -> ``(counts, sums)``: int32
+    ``[n, 2, 11]`` in ``SURFACE_COLUMNS`` order and float64 ``[n, 2]``, per image and side (side 0 measures from the first
+    region's edge to the second's, side 1 the other way).  ``utils.compare_metrics.surface_metrics`` turns them into Hausdorff,
+    its percentile form, the average symmetric surface distance and surface Dice.
+
+    ``masks`` alone: contiguous uint8 ``[n, h, w]`` as ``mask_compare(..., masks=True)`` writes it, bit 0 the first region and
+    bit 1 the second.  With ``other``: two uint8 / bool ``[n, h, w]`` tensors, any non-zero byte is foreground.  ``1 <= h, w <=
+    MASK_COMPARE_MAX_EDGE``.  An edge pixel is a foreground pixel with a 4-neighbour that is background or outside the image;
+    ``d2`` of an edge pixel is its exact squared distance to the nearest edge pixel of the other region.  ``percentile``: a
+    multiple of 0.1; ``d2_lo`` / ``d2_hi`` are the two order statistics it is interpolated between.  ``tolerances``: up to four
+    distances in pixels, ``within_j`` counts the edge pixels within each.  If either region of an image has no edge pixel both
+    its rows hold ``-1`` for the three ``d2`` columns and 0 elsewhere (``n_fg``, ``n_edge`` stay true).  ``out=(counts, sums)``
+    are written in place.  Three launches on the current stream, no host sync; every integer is exact and the output is
+    bitwise reproducible; the scratch buffer (12 bytes per pixel and image) is cached per (stream, shape)."""
+    who = "surface_distance"
+    pair = [("masks", masks)] + ([("other", other)] if other is not None else [])
+    for name, t in pair:
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.bool):
+            raise TypeError(f"{who}: {name} must be a uint8 tensor, got {getattr(t, 'dtype', type(t))}")
+        if not t.is_cuda or t.device != masks.device:
+            raise ValueError(f"{who}: {name} must be a CUDA(HIP) tensor on the device of masks")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+    if masks.dim() != 3 or (other is not None and other.shape != masks.shape):
+        raise ValueError(f"{who}: expected [n, h, w] masks of one shape, got {tuple(masks.shape)}"
+                         + (f" / {tuple(other.shape)}" if other is not None else ""))
+    n, h, w = masks.shape
+    if not (1 <= n <= 32767 and 1 <= h <= MASK_COMPARE_MAX_EDGE and 1 <= w <= MASK_COMPARE_MAX_EDGE):
+        raise ValueError(f"{who}: unsupported shape {tuple(masks.shape)} (1 <= n <= 32767, 1 <= h, w <= {MASK_COMPARE_MAX_EDGE})")
+    pm = surface_percentile_pm(who, percentile)
+    tol = surface_tolerances_d2(who, tolerances)
+    out = _outs(who, out, ("counts", "sums"))
+    counts = _out(out[0], (n, 2, len(SURFACE_COLUMNS)), torch.int32, masks.device, f"{who}: out[0] (counts)")
+    sums = _out(out[1], (n, 2), torch.float64, masks.device, f"{who}: out[1] (sums)")
+    stream = _stream()
+    ws, ws_bytes = _scratch_bytes(who, "surface_distance", (n, h, w), L.lib().pti_surface_distance_ws_bytes(n, h, w),
+                                  tuple(masks.shape), masks.device, stream)
+    a, b, a_bits, b_bits = (masks, masks, 1, 2) if other is None else (masks, other, 255, 255)
+    L.check(L.lib().pti_surface_distance(_ptr(a), a_bits, _ptr(b), b_bits, n, h, w, pm, (C.c_int32 * max(len(tol), 1))(*tol),
+                                         len(tol), _ptr(counts), _ptr(sums), _ptr(ws), ws_bytes, stream), "pti_surface_distance")
+    return counts, sums
 
 
 # ---- pair registration: straighten, then align (csrc/mask_compare.hip; include/pti_vae.h "pair registration") -------------

@@ -5,6 +5,10 @@ reference's five outlier counts, the twelve threshold counts and the rows of its
 ``pair_metrics(..., ssim=...)`` adds the reference's ``"SSIM"`` row from ``ops.ssim_uniform``'s two numbers per pair (skimage's
 uniform-window SSIM of the ground truth and the cleaned prediction); without the argument nothing changes.
 
+``surface_metrics`` turns the integer table and the sums of ``ops.surface_distance`` into the boundary distances of a pair
+(Hausdorff, its percentile form, the average symmetric surface distance, surface Dice), and
+``pair_metrics(..., surface=...)`` appends them; without the argument nothing changes.
+
 What is not here: the VGG16 cosine similarity and Euclidean distance; the straighten / align step that the
 reference runs before measuring happens on the device before these numbers are taken."""
 from __future__ import annotations
@@ -14,6 +18,7 @@ import math
 import numpy as np
 
 from .._lib import MASK_COMPARE_COLUMNS as COLUMNS
+from .._lib import SURFACE_COLUMNS
 
 METRIC_KEYS = ("MSE", "PSNR", "Dice Coefficient", "Dice Loss", "IoU", "Height Metric", "Width Metric Upper",
                "Width Metric Middle", "Width Metric Lower", "Absolute Height Difference", "Absolute Width Upper Difference",
@@ -24,6 +29,8 @@ HIGHER_IS_BETTER = frozenset(("PSNR", "Dice Coefficient", "Height Metric", "Widt
 # the optional row of ``pair_metrics(..., ssim=...)`` is higher-is-better too; kept apart so that the set above stays the
 # flagless report's
 HIGHER_IS_BETTER_OPTIONAL = frozenset(("SSIM",))
+# ... and so is every optional key that starts with one of these (``surface_metrics``: one key per tolerance)
+HIGHER_IS_BETTER_OPTIONAL_PREFIXES = ("Surface Dice @ ",)
 SSIM_MIN_EDGE = 7   # the uniform window of ``ops.ssim_uniform``: a smaller image has no SSIM
 OUTLIER_KEYS = ("outside_1_ci", "outside_2_ci", "outside_3_ci", "outside_iqr", "outside_z")
 DIMENSION_COLUMNS = ("Image Path", "GT Height", "GT Width Upper", "GT Width Middle", "GT Width Lower", "Gen Height",
@@ -50,13 +57,85 @@ def dimensions(row) -> dict:
             "Gen Width Middle": c["pred_width_middle"], "Gen Width Lower": c["pred_width_lower"]}
 
 
-def pair_metrics(counts, sums, h: int, w: int, ssim=None) -> list:
+def surface_keys(tolerances, percentile_pm: int) -> tuple:
+    """The keys of ``surface_metrics`` in order: ``"Hausdorff Distance"``, ``"Hausdorff Distance 95"`` (the percentile as given),
+    ``"Average Surface Distance"``, then ``"Surface Dice @ {t} px"`` per tolerance."""
+    return ("Hausdorff Distance", f"Hausdorff Distance {percentile_pm / 10:g}", "Average Surface Distance") \
+        + tuple(f"Surface Dice @ {float(t):g} px" for t in tolerances)
+
+
+def _surface_sides(counts, sums, percentile_pm: int):
+    """One image's two rows -> per side ``{n_edge, max, percentile, mean}`` in pixels; the last three ``None`` on an empty side
+    (the kernel marks both rows then).  A non-zero status column raises."""
+    out = []
+    for row, total in zip(counts, sums):
+        c = dict(zip(SURFACE_COLUMNS, (int(v) for v in row)))
+        if c["status"] != 0:
+            raise RuntimeError(f"surface_metrics: surface_distance reported status {c['status']}")
+        m = c["n_edge"]
+        if m == 0 or c["max_d2"] < 0:
+            out.append({"n_edge": m, "max": None, "percentile": None, "mean": None, "within": None})
+            continue
+        lo, hi = math.sqrt(c["d2_lo"]), math.sqrt(c["d2_hi"])
+        frac = (((m - 1) * percentile_pm) % 1000) / 1000.0
+        out.append({"n_edge": m, "max": math.sqrt(c["max_d2"]), "percentile": lo + frac * (hi - lo), "mean": float(total) / m,
+                    "within": [c[f"within_{j}"] for j in range(4)], "sum": float(total)})
+    return out
+
+
+def surface_block(counts, sums, percentile_pm: int) -> dict:
+    """The ``"surface"`` entry of one image in ``compare_metrics.json``: both directed maxima, percentile values and means (side
+    0 from the ground truth's outline to the prediction's, side 1 the other way) and both edge counts, in pixels."""
+    g, p = _surface_sides(counts, sums, percentile_pm)
+    return {"percentile": percentile_pm / 10, "edge_pixels_gt": g["n_edge"], "edge_pixels_pred": p["n_edge"],
+            "max_gt_to_pred": g["max"], "max_pred_to_gt": p["max"], "percentile_gt_to_pred": g["percentile"],
+            "percentile_pred_to_gt": p["percentile"], "mean_gt_to_pred": g["mean"], "mean_pred_to_gt": p["mean"]}
+
+
+def surface_metrics(counts, sums, tolerances, percentile_pm: int) -> list:
+    """Per pair the boundary distances, in pixels, from ``ops.surface_distance``'s ``counts`` int ``[n, 2, 11]`` and ``sums``
+    float64 ``[n, 2]`` (host arrays); ``tolerances`` are the pixel distances the launch was given, ``percentile_pm`` its
+    percentile in per-mille.  With ``m_s`` the edge pixels of side ``s``:
+
+    * ``"Hausdorff Distance"``: ``sqrt(max(max_d2 of both sides))``;
+    * ``"Hausdorff Distance 95"``: per side ``sqrt(d2_lo) + frac (sqrt(d2_hi) - sqrt(d2_lo))``, ``frac = (((m - 1) pm) % 1000) /
+      1000`` -- numpy's linear percentile of the side's distances -- and the larger of the two sides;
+    * ``"Average Surface Distance"``: ``(sum_0 + sum_1) / (m_0 + m_1)``, the pooled symmetric mean;
+    * ``"Surface Dice @ {t} px"``: ``(within_0j + within_1j) / (m_0 + m_1)`` -- edge PIXELS within the tolerance, not surfel
+      lengths.
+
+    All of them are ``None`` when a side has no edge pixel."""
+    counts = np.asarray(counts).reshape(-1, 2, len(SURFACE_COLUMNS))
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1, 2)
+    if len(counts) != len(sums):
+        raise ValueError(f"surface_metrics: {len(counts)} count rows but {len(sums)} sum rows")
+    tolerances = list(tolerances)
+    if len(tolerances) > 4:
+        raise ValueError(f"surface_metrics: at most 4 tolerances, got {len(tolerances)}")
+    keys = surface_keys(tolerances, percentile_pm)
+    out = []
+    for c, s in zip(counts, sums):
+        a, b = _surface_sides(c, s, percentile_pm)
+        if a["max"] is None or b["max"] is None:
+            out.append(dict.fromkeys(keys))
+            continue
+        m = a["n_edge"] + b["n_edge"]
+        values = [max(a["max"], b["max"]), max(a["percentile"], b["percentile"]), (a["sum"] + b["sum"]) / m]
+        values += [(a["within"][j] + b["within"][j]) / m for j in range(len(tolerances))]
+        out.append(dict(zip(keys, values)))
+    return out
+
+
+def pair_metrics(counts, sums, h: int, w: int, ssim=None, surface=None) -> list:
     """Per image either the metric dictionary (``METRIC_KEYS`` in order) or, for a pair that is skipped, the reason as a
     string: a side without any foreground component has no box to measure (the reference's ``except`` drops such a pair).
 
     ``ssim``: float64 ``[n, 2]`` = ``{ssim, data range}`` as ``ops.ssim_uniform`` returns them (host array); every dictionary
     then carries ``"SSIM"`` right after ``"MSE"`` (the reference's order).  It is ``None`` when the data range is 0 (a constant
     ground truth: 0 / 0) or when an edge is below ``SSIM_MIN_EDGE`` (no 7 x 7 window fits); such a pair keeps its other metrics.
+
+    ``surface``: ``(counts, sums, tolerances, percentile_pm)`` as ``surface_metrics`` takes them; its keys are appended after
+    the existing ones.
 
     ``counts`` int ``[n, 24]`` / ``sums`` float64 ``[n, 3]`` as ``ops.mask_compare`` returns them (host arrays), ``h, w`` the
     image size.  PSNR is ``inf`` at MSE 0 and ``None`` when neither image has a positive pixel; a ratio is ``None`` when
@@ -72,6 +151,10 @@ def pair_metrics(counts, sums, h: int, w: int, ssim=None) -> list:
         ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 2)
         if len(ssim) != len(counts):
             raise ValueError(f"pair_metrics: {len(counts)} count rows but {len(ssim)} ssim rows")
+    if surface is not None:
+        surface = surface_metrics(*surface)
+        if len(surface) != len(counts):
+            raise ValueError(f"pair_metrics: {len(counts)} count rows but {len(surface)} surface rows")
     out = []
     for i, (row, (sq, max_gt, max_pred)) in enumerate(zip(counts, sums)):
         c = dict(zip(COLUMNS, (int(v) for v in row)))
@@ -99,6 +182,8 @@ def pair_metrics(counts, sums, h: int, w: int, ssim=None) -> list:
         if ssim is not None:
             value = None if (ssim[i][1] == 0 or min(int(h), int(w)) < SSIM_MIN_EDGE) else float(ssim[i][0])
             m = {"MSE": m.pop("MSE"), "SSIM": value, **m}
+        if surface is not None:
+            m.update(surface[i])
         out.append(m)
     return out
 
@@ -134,7 +219,8 @@ def aggregate(all_metrics: list) -> dict:
                 "outside_iqr": int(np.sum((data < q1 - 1.5 * iqr) | (data > q3 + 1.5 * iqr))),
                 "outside_z": 0 if std == 0 else int(np.sum(np.abs((data - mean) / std) > 3)),
             }
-        worst = float(data.min() if key in HIGHER_IS_BETTER or key in HIGHER_IS_BETTER_OPTIONAL else data.max())
+        higher = key in HIGHER_IS_BETTER or key in HIGHER_IS_BETTER_OPTIONAL or key.startswith(HIGHER_IS_BETTER_OPTIONAL_PREFIXES)
+        worst = float(data.min() if higher else data.max())
         out[key] = {"n": n, "none": none, "mean": mean, "std": std, "ci95": [lo, hi], "worst": worst, "outliers": outliers}
     return out
 
