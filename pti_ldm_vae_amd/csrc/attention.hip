@@ -484,10 +484,22 @@ static int attn_check(const char* who, int b, int l, int c) {
   return 0;
 }
 
+// C^-1/2 and log2(e) C^-1/2 as fp32, each rounded ONCE from the double value.  They were `1.0f / sqrtf(c)` on the host, which
+// this library's -ffast-math build turns into a reciprocal-square-root ESTIMATE plus one Newton step: exact on one x86 CPU,
+// 0.124999993 for C = 64 (and one ulp low at 128 and 256 as well) on another, as each CPU's estimate table has it.  The
+// scale of softmax(q k^T C^-1/2) must not depend on the host, and the exact tests (tests/attention_oracle.py) need it to
+// the bit: a table of the three supported head dims, no run-time arithmetic.
+static void attn_scales(int c, float* scale, float* c_log2) {
+  const double s = c == 64 ? 0.125 : c == 128 ? 0.08838834764831845 : 0.0625;
+  *scale = (float)s;
+  *c_log2 = (float)(1.4426950408889634 * s);
+}
+
 extern "C" int pti_attention_fwd(const void* qkv, void* o, float* lse2, int b, int l, int c, pti_stream_t s) {
   if (!qkv || !o || !lse2) PTI_FAIL(PTI_EINVAL, "attention_fwd: null pointer");
   if (int rc = attn_check("attention_fwd", b, l, c)) return rc;
-  const float c_log2 = 1.4426950408889634f / sqrtf((float)c);
+  float scale, c_log2;
+  attn_scales(c, &scale, &c_log2);
   dim3 grid((l + TB - 1) / TB, b), blk(64 * NW);
   hipStream_t st = (hipStream_t)s;
   if (c == 64) PTI_LAUNCH(attn_fwd_kernel<64>, grid, blk, 0, st, (const bf16*)qkv, (bf16*)o, lse2, l, c_log2);
@@ -501,7 +513,8 @@ extern "C" int pti_attention_bwd(const void* qkv, const void* o, const void* dou
                                  void* dqkv, int b, int l, int c, pti_stream_t s) {
   if (!qkv || !o || !dout || !lse2 || !delta || !dqkv) PTI_FAIL(PTI_EINVAL, "attention_bwd: null pointer");
   if (int rc = attn_check("attention_bwd", b, l, c)) return rc;
-  const float scale = 1.0f / sqrtf((float)c), c_log2 = 1.4426950408889634f * scale;
+  float scale, c_log2;
+  attn_scales(c, &scale, &c_log2);
   hipStream_t st = (hipStream_t)s;
   const long long rows = (long long)b * l;
   long long db = (rows + (256 / (c / 8)) - 1) / (256 / (c / 8));
