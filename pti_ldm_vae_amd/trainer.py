@@ -31,6 +31,11 @@ from .engine import capture_or_eager
 from .optim import FlatAdam
 
 
+# what VAETrainer._forward_loss hands on: the [recon, kl] pair, the forward's tensors, the encoder's and decoder's
+# backward contexts and the loss kernel's three gradients (contexts and gradients None without ``train``)
+_Forward = collections.namedtuple("_Forward", "out2 recon mu sigma eps c_enc c_dec d_recon d_mu d_third")
+
+
 def prepare_batch(batch, device, ar_vae_enabled: bool):
     """Reference ``_prepare_batch`` (train_vae.py:183-243): -> ``(images on device, attributes dict on device | None)``.
 
@@ -288,126 +293,153 @@ class VAETrainer:
         d_recon.add_(g, alpha=self.perceptual_weight)
         return p.detach()
 
-    def _plain_fwd_dec_bwd(self, images, eps, join):
-        """First half of the plain step: zero_grad -> forward -> L1|L2 + kl_weight*KL -> DECODER backward, without any
-        optional term and without host-side decisions.  ``join``: wait for the side-stream weight gradients, so that the
-        post_quant + decoder region of the gradient arena is final when this returns (the data-parallel graph mode
-        all-reduces it between its two captured halves).  Returns (the [recon, kl] device pair, what the second half needs)."""
+    # ---- the step's bodies: eager launches and graph captures run these same lines ----------------------------------
+    def _forward_loss(self, images, eps, *, train: bool):
+        """forward (encode, sample, decode) -> L1|L2 + kl_weight*KL, without any optional term.  ``eps`` None: drawn from
+        ``self.gen``.  ``train``: keep what the backward needs and have the loss kernel write its three gradients."""
         net, eng = self.net, self.eng
-        net.grad_arena.zero_()
-        mu, sigma, c_enc = eng.encode_forward(images, save=True)
-        z = torch.addcmul(mu, eps, sigma)
-        recon, c_dec = eng.decode_forward(z, save=True)
+        mu, sigma, c_enc = eng.encode_forward(images, save=train)
+        if eps is None:
+            eps = torch.randn(sigma.shape, generator=self.gen, device=sigma.device, dtype=sigma.dtype)
+        recon, c_dec = eng.decode_forward(torch.addcmul(mu, eps, sigma), save=train)
         third = sigma if net.third_output == "sigma" else 2.0 * torch.log(sigma)
         out2 = torch.zeros(2, dtype=torch.float32, device=recon.device)
-        d_recon, d_mu, d_third = torch.empty_like(recon), torch.empty_like(mu), torch.empty_like(third)
-        ops.vae_loss(recon, images, mu, third, out2, d_recon, d_mu, d_third, l2=self.l2, third_mode=self.third_mode,
-                     kl_weight=self.kl_weight)
-        dz = eng.decode_backward(c_dec, d_recon, want_dz=True, join=join)
-        d_sigma = d_third if net.third_output == "sigma" else d_third * (2.0 / sigma)
-        d_mu = d_mu + dz
-        d_sigma = torch.addcmul(d_sigma, dz, eps)
-        return out2, (c_enc, d_mu, d_sigma)
+        d_recon = d_mu = d_third = None
+        if train:
+            d_recon, d_mu, d_third = torch.empty_like(recon), torch.empty_like(mu), torch.empty_like(third)
+        ops.vae_loss(recon, images.contiguous().float(), mu, third, out2, d_recon, d_mu, d_third, l2=self.l2,
+                     third_mode=self.third_mode, kl_weight=self.kl_weight)
+        return _Forward(out2, recon, mu, sigma, eps, c_enc, c_dec, d_recon, d_mu, d_third)
 
-    def _plain_enc_bwd(self, carry):
-        """Second half: the ENCODER backward (joins the side stream)."""
+    def _optional_terms(self, fwd, images, attributes, adversarial, with_p, p_target):
+        """The step's optional terms, between the loss and the backward: AR-VAE into ``fwd.d_mu``, perceptual and
+        adversarial into ``fwd.d_recon``.  -> (ar_out, p_loss, adv_gen, adv_ctx, adv_disc, adv_done), None where off;
+        ``adv_done`` None with ``adversarial``: the discriminator's step is still to run (no stream of its own)."""
+        recon, d_recon = fwd.recon, fwd.d_recon
+        ar_out = None
+        if self.ar is not None:   # + gamma * AR-VAE(z_mu.mean(h, w)): its gradient goes straight into d_mu
+            ar_out = self._ar_term(fwd.mu, attributes, fwd.d_mu)
+        p_loss = None
+        adv_gen = adv_ctx = adv_disc = adv_done = None
+        if adversarial and with_p and self._adv_stream is not None:
+            # both optional terms depend on the reconstruction only: the generator's adversarial term runs on the
+            # discriminator's stream (followed there by the discriminator's own step) while the perceptual term
+            # runs here; the gradients join in the serial schedule's order, (VAE + perceptual) + adversarial
+            main, advs = torch.cuda.current_stream(), self._adv_stream
+            advs.wait_stream(main)
+            with torch.cuda.stream(advs):
+                d_adv = torch.empty_like(d_recon)
+                adv_gen, adv_ctx = self._adv_generator_term(recon, d_adv, accumulate=False)
+                g_done = torch.cuda.Event()
+                g_done.record(advs)
+                adv_disc = self._adv_discriminator_losses(adv_ctx, images, train=True)
+                adv_done = torch.cuda.Event()
+                adv_done.record(advs)
+            for t in (d_adv, adv_gen, adv_disc):
+                t.record_stream(main)
+            p_loss = self._perceptual_term(recon, images, d_recon, p_target)
+            main.wait_event(g_done)
+            d_recon.add_(d_adv)
+        else:
+            if with_p:
+                p_loss = self._perceptual_term(recon, images, d_recon, p_target)
+            if adversarial:       # + adv_weight * generator term: its gradient w.r.t. the reconstruction joins d_recon
+                adv_gen, adv_ctx = self._adv_generator_term(recon, d_recon)
+                if self._adv_stream is not None:     # the discriminator's step, on its stream, under the VAE backward
+                    main = torch.cuda.current_stream()
+                    self._adv_stream.wait_stream(main)
+                    with torch.cuda.stream(self._adv_stream):
+                        adv_disc = self._adv_discriminator_losses(adv_ctx, images, train=True)
+                        adv_done = torch.cuda.Event()
+                        adv_done.record(self._adv_stream)
+                    adv_disc.record_stream(main)
+        return ar_out, p_loss, adv_gen, adv_ctx, adv_disc, adv_done
+
+    def _decoder_backward(self, fwd, join):
+        """DECODER backward and the reparameterisation's.  ``join``: wait for the side-stream weight gradients, so that
+        the post_quant + decoder region of the gradient arena is final when this returns (the data-parallel graph mode
+        all-reduces it between its two captured halves); otherwise ``_encoder_backward``'s join covers the side stream.
+        Returns what ``_encoder_backward`` needs."""
+        dz = self.eng.decode_backward(fwd.c_dec, fwd.d_recon, want_dz=True, join=join)
+        # z = mu + eps*sigma ; third = sigma (or 2 log sigma)
+        d_sigma = fwd.d_third if self.net.third_output == "sigma" else fwd.d_third * (2.0 / fwd.sigma)
+        d_mu = fwd.d_mu + dz
+        d_sigma = torch.addcmul(d_sigma, dz, fwd.eps)
+        return fwd.c_enc, d_mu, d_sigma
+
+    def _encoder_backward(self, carry):
+        """The ENCODER backward (joins the side stream)."""
         c_enc, d_mu, d_sigma = carry
         self.eng.encode_backward(c_enc, d_mu, d_sigma, want_dx=False)
 
-    def _plain_fwd_bwd(self, images, eps):
-        """The part of the plain step ONE HIP graph can hold (single GPU).  Returns the [recon, kl] device pair."""
-        out2, carry = self._plain_fwd_dec_bwd(images, eps, join=False)    # encode_backward's join covers the side stream
-        self._plain_enc_bwd(carry)
-        return out2
+    def _step_graphed(self, images, eps):
+        """zero_grad, forward, loss, backward and gradient exchange of one plain step through captured graphs (see
+        ``step_graph``) -> the [recon, kl] device pair; None when this call must run eagerly: the first two steps (they
+        settle the lazily built state), more than four captured batch shapes, per-kernel profiling, a failed capture.
+        One GPU: ONE graph.  Data parallel (world > 1): TWO graphs with the collectives eager between them --
+        [forward, loss, decoder backward] | all-reduce of the post_quant + decoder region in ~bucket-sized asynchronous
+        pieces | [encoder backward] | all-reduce of the encoder + quant region | join.  The decoder region's exchange
+        (3/4 of the gradient bytes of config A) runs under the second graph, as the eager callbacks arrange it; what the
+        graphs remove is the eager step's ~5 ms of host enqueue per rank, which at N = 8 is no longer hidden behind a
+        single process's GPU time.
+        EVERY RANK MUST TAKE THE SAME PATH on the same step (the two paths cut the arena into different buckets): the
+        decision here and in ``step`` depends only on state that is identical across ranks in a symmetric job -- the step
+        count, the batch shape, ``step_graph`` -- plus ``ops.KERNEL_PROFILE``, which a caller that profiles one rank must
+        pair with ``step_graph = False`` on all of them (bench.py does)."""
+        net, dp = self.net, self.world > 1
+        # everything the captured launches bake in besides the weights: shape, loss settings, stream layout
+        key = ("dp" if dp else "one", tuple(images.shape), self.l2, self.kl_weight, self.third_mode,
+               self.eng.wgrad_stream is None, self.eng.wgrad_batch_max)
+        st = self._graphs.get(key)
+        if st is None:
+            if self._eager_steps < 2 or len(self._graphs) >= 4 or ops.KERNEL_PROFILE is not None:
+                return None
+            down = 2 ** (len(net.channels) - 1)
+            gx = images.detach().float().contiguous().clone()
+            geps = torch.zeros(images.shape[0], net.latent_channels, images.shape[2] // down, images.shape[3] // down,
+                               dtype=torch.float32, device=images.device)
 
-    def _capture_inputs(self, images):
-        """Static inputs (gx, geps) of a step capture for this batch shape; None when this call must run eagerly: the
-        first two steps (they settle the lazily built state), more than four captured shapes, or per-kernel profiling."""
-        if self._eager_steps < 2 or len(self._graphs) >= 4 or ops.KERNEL_PROFILE is not None:
-            return None
-        net = self.net
-        down = 2 ** (len(net.channels) - 1)
-        gx = images.detach().float().contiguous().clone()
-        geps = torch.zeros(images.shape[0], net.latent_channels, images.shape[2] // down, images.shape[3] // down,
-                           dtype=torch.float32, device=images.device)
-        return gx, geps
+            def first():                      # one GPU: the whole step; data parallel: up to the seam
+                net.grad_arena.zero_()
+                fwd = self._forward_loss(gx, geps, train=True)
+                out2, carry = fwd.out2, self._decoder_backward(fwd, join=dp)
+                del fwd                       # the decoder's saved activations are not held across the encoder backward
+                if dp:
+                    return out2, carry
+                self._encoder_backward(carry)
+                return out2, None
 
-    def _fill_inputs(self, gx, geps, images, eps):
+            torch.cuda.synchronize()
+            # the weight re-pack launches must be PART of the (first) graph (every replay follows an optimiser step): if
+            # a no_grad forward (validation, eval_losses) ran just before this call the packs are clean and
+            # refresh_weights() would return early during capture -- every replay would then train on the weights as
+            # last packed eagerly (ADVICE r2, medium).  Force the dirty state for the capture.
+            self.eng.packed_version = -1
+            self.eng.grad_ready_cb = None
+            bodies = (first, lambda one: self._encoder_backward(one[1])) if dp else (first,)
+            captured = capture_or_eager("the data-parallel step" if dp else "the training step", *bodies)
+            if captured is None:
+                self.step_graph = False
+                return None
+            graphs, ((out2, carry), *_) = captured
+            st = self._graphs[key] = (graphs, gx, geps, out2, carry)     # `carry` keeps the tensors crossing the seam alive
+        graphs, gx, geps, out2, _ = st
         gx.copy_(images)
         if eps is None:
             geps.normal_(generator=self.gen)        # the same draws torch.randn(..., generator=self.gen) makes eagerly
         else:
             geps.copy_(eps)
-
-    def _step_graphed(self, images, eps):
-        """One plain step through a captured graph (see ``step_graph``); None when this call must run eagerly (the first
-        two steps, which settle the lazily built state, and more than four batch shapes)."""
-        # everything the captured launches bake in besides the weights: shape, loss settings, stream layout
-        key = (tuple(images.shape), self.l2, self.kl_weight, self.third_mode, self.eng.wgrad_stream is None,
-               self.eng.wgrad_batch_max)
-        st = self._graphs.get(key)
-        if st is None:
-            inputs = self._capture_inputs(images)
-            if inputs is None:
-                return None
-            gx, geps = inputs
-            torch.cuda.synchronize()
-            # the weight re-pack launches must be PART of the graph (every replay follows an optimiser step): if a
-            # no_grad forward (validation, eval_losses) ran just before this call the packs are clean and
-            # refresh_weights() would return early during capture -- every replay would then train on the weights as
-            # last packed eagerly (ADVICE r2, medium).  Force the dirty state for the capture.
-            self.eng.packed_version = -1
-            captured = capture_or_eager("the training step", lambda: self._plain_fwd_bwd(gx, geps))
-            if captured is None:
-                self.step_graph = False
-                return None
-            (g,), (out2,) = captured
-            st = self._graphs[key] = (g, gx, geps, out2)
-        g, gx, geps, out2 = st
-        self._fill_inputs(gx, geps, images, eps)
-        g.replay()
-        return out2.clone()
-
-    def _step_graphed_dp(self, images, eps):
-        """Data-parallel form of ``_step_graphed`` (world > 1): the step is captured as TWO graphs with the collectives
-        eager between them -- [forward, loss, decoder backward] | all-reduce of the post_quant + decoder region in
-        ~bucket-sized asynchronous pieces | [encoder backward] | all-reduce of the encoder + quant region | join | Adam.
-        The decoder region's exchange (3/4 of the gradient bytes of config A) runs under the second graph, as the eager
-        callbacks arrange it; what the graphs remove is the eager step's ~5 ms of host enqueue per rank, which at N = 8
-        is no longer hidden behind a single process's GPU time.  None when this call must run eagerly.
-        EVERY RANK MUST TAKE THE SAME PATH on the same step (the two paths cut the arena into different buckets): the
-        decision below depends only on state that is identical across ranks in a symmetric job -- the step count, the batch
-        shape, ``step_graph`` -- plus ``ops.KERNEL_PROFILE``, which a caller that profiles one rank must pair with
-        ``step_graph = False`` on all of them (bench.py does)."""
-        key = ("dp", tuple(images.shape), self.l2, self.kl_weight, self.third_mode, self.eng.wgrad_stream is None,
-               self.eng.wgrad_batch_max)
-        st = self._graphs.get(key)
-        if st is None:
-            inputs = self._capture_inputs(images)
-            if inputs is None:
-                return None
-            gx, geps = inputs
-            torch.cuda.synchronize()
-            self.eng.packed_version = -1          # the re-pack launches are part of the first graph (see _step_graphed)
-            self.eng.grad_ready_cb = None
-            captured = capture_or_eager("the data-parallel step",
-                                        lambda: self._plain_fwd_dec_bwd(gx, geps, join=True),
-                                        lambda first: self._plain_enc_bwd(first[1]))
-            if captured is None:
-                self.step_graph = False
-                return None
-            (ga, gb), ((out2, carry), _) = captured
-            st = self._graphs[key] = (ga, gb, gx, geps, out2, carry)     # `carry` keeps the tensors crossing the seam alive
-        ga, gb, gx, geps, out2, _ = st
-        self._fill_inputs(gx, geps, images, eps)
-        red = self.reducer
-        (e_lo, e_hi), (d_lo, d_hi) = self.net.arena_regions()
-        red.begin_step()
-        ga.replay()
-        red.reduce_range(d_lo, d_hi)          # asynchronous: runs under the second graph
-        gb.replay()
-        red.reduce_range(e_lo, e_hi)
-        red.finish()
+        if dp:
+            red = self.reducer
+            (e_lo, e_hi), (d_lo, d_hi) = net.arena_regions()
+            red.begin_step()
+            graphs[0].replay()
+            red.reduce_range(d_lo, d_hi)          # asynchronous: runs under the second graph
+            graphs[1].replay()
+            red.reduce_range(e_lo, e_hi)
+            red.finish()
+        else:
+            graphs[0].replay()
         return out2.clone()
 
     def step(self, images: torch.Tensor, eps: torch.Tensor | None = None, attributes: dict | None = None,
@@ -424,84 +456,29 @@ class VAETrainer:
         net, eng, red = self.net, self.eng, self.reducer
         while len(self._step_done) >= max(1, self.max_steps_in_flight):
             self._step_done.popleft().synchronize()
-        plain = (self.world == 1 and self.ar is None and not adversarial
-                 and not (self.perceptual is not None and self.perceptual_weight != 0.0))
+        with_p = self.perceptual is not None and self.perceptual_weight != 0.0
+        plain = self.ar is None and not adversarial and not with_p
         use_graph = self.step_graph is True or (self.step_graph == "auto" and images.shape[0] * images.shape[2] * images.shape[3] <= 6 * 65536)
-        plain_dp = (self.world > 1 and self.ar is None and not adversarial
-                    and not (self.perceptual is not None and self.perceptual_weight != 0.0))
-        if use_graph and (plain or plain_dp) and ops.KERNEL_PROFILE is None:
-            out2 = self._step_graphed(images, eps) if plain else self._step_graphed_dp(images, eps)
-            if out2 is not None:
-                self.opt.step(grad_scale=1.0 / self.world)
-                done = torch.cuda.Event()
-                done.record()
-                self._step_done.append(done)
-                return {"loss": out2[0] + self.kl_weight * out2[1], "recon": out2[0], "kl": out2[1]}
-        self._eager_steps += 1
-        net.grad_arena.zero_()
-        red.begin_step()
-        eng.grad_ready_cb = red.ready if self.world > 1 else None
-        try:
-            p_target = None
-            if self.perceptual is not None and self.perceptual_weight != 0.0:
-                p_target = self._perceptual_target_taps(images)     # side stream, under the VAE forward
-            mu, sigma, c_enc = eng.encode_forward(images, save=True)
-            if eps is None:
-                eps = torch.randn(sigma.shape, generator=self.gen, device=sigma.device, dtype=sigma.dtype)
-            z = torch.addcmul(mu, eps, sigma)
-            recon, c_dec = eng.decode_forward(z, save=True)
-            third = sigma if net.third_output == "sigma" else 2.0 * torch.log(sigma)
-            out2 = torch.zeros(2, dtype=torch.float32, device=recon.device)
-            d_recon, d_mu, d_third = torch.empty_like(recon), torch.empty_like(mu), torch.empty_like(third)
-            ops.vae_loss(recon, images.contiguous().float(), mu, third, out2, d_recon, d_mu, d_third, l2=self.l2,
-                         third_mode=self.third_mode, kl_weight=self.kl_weight)
-            ar_out = None
-            if self.ar is not None:   # + gamma * AR-VAE(z_mu.mean(h, w)): its gradient goes straight into d_mu
-                ar_out = self._ar_term(mu, attributes, d_mu)
-            p_loss = None
-            with_p = self.perceptual is not None and self.perceptual_weight != 0.0
-            adv_ctx = adv_disc = adv_done = None
-            if adversarial and with_p and self._adv_stream is not None:
-                # both optional terms depend on the reconstruction only: the generator's adversarial term runs on the
-                # discriminator's stream (followed there by the discriminator's own step) while the perceptual term
-                # runs here; the gradients join in the serial schedule's order, (VAE + perceptual) + adversarial
-                main, advs = torch.cuda.current_stream(), self._adv_stream
-                advs.wait_stream(main)
-                with torch.cuda.stream(advs):
-                    d_adv = torch.empty_like(d_recon)
-                    adv_gen, adv_ctx = self._adv_generator_term(recon, d_adv, accumulate=False)
-                    g_done = torch.cuda.Event()
-                    g_done.record(advs)
-                    adv_disc = self._adv_discriminator_losses(adv_ctx, images, train=True)
-                    adv_done = torch.cuda.Event()
-                    adv_done.record(advs)
-                for t in (d_adv, adv_gen, adv_disc):
-                    t.record_stream(main)
-                p_loss = self._perceptual_term(recon, images, d_recon, p_target)
-                main.wait_event(g_done)
-                d_recon.add_(d_adv)
-            else:
-                if with_p:
-                    p_loss = self._perceptual_term(recon, images, d_recon, p_target)
-                if adversarial:       # + adv_weight * generator term: its gradient w.r.t. the reconstruction joins d_recon
-                    adv_gen, adv_ctx = self._adv_generator_term(recon, d_recon)
-                    if self._adv_stream is not None:     # the discriminator's step, on its stream, under the VAE backward
-                        main = torch.cuda.current_stream()
-                        self._adv_stream.wait_stream(main)
-                        with torch.cuda.stream(self._adv_stream):
-                            adv_disc = self._adv_discriminator_losses(adv_ctx, images, train=True)
-                            adv_done = torch.cuda.Event()
-                            adv_done.record(self._adv_stream)
-                        adv_disc.record_stream(main)
-            dz = eng.decode_backward(c_dec, d_recon, want_dz=True, join=False)   # encode_backward joins the side stream
-            # z = mu + eps*sigma ; third = sigma (or 2 log sigma)
-            d_sigma = d_third if net.third_output == "sigma" else d_third * (2.0 / sigma)
-            d_mu = d_mu + dz
-            d_sigma = torch.addcmul(d_sigma, dz, eps)
-            eng.encode_backward(c_enc, d_mu, d_sigma, want_dx=False)
-            red.finish()
-        finally:
-            eng.grad_ready_cb = None
+        out2 = ar_out = p_loss = None
+        if use_graph and plain and ops.KERNEL_PROFILE is None:
+            out2 = self._step_graphed(images, eps)
+        if out2 is None:
+            self._eager_steps += 1
+            net.grad_arena.zero_()
+            red.begin_step()
+            eng.grad_ready_cb = red.ready if self.world > 1 else None
+            try:
+                # the target half of the perceptual term: side stream, under the VAE forward
+                p_target = self._perceptual_target_taps(images) if with_p else None
+                fwd = self._forward_loss(images, eps, train=True)
+                out2 = fwd.out2
+                ar_out, p_loss, adv_gen, adv_ctx, adv_disc, adv_done = self._optional_terms(
+                    fwd, images, attributes, adversarial, with_p, p_target)
+                carry = self._decoder_backward(fwd, join=False)
+                self._encoder_backward(carry)
+                red.finish()
+            finally:
+                eng.grad_ready_cb = None
         self.opt.step(grad_scale=1.0 / self.world)
         if adversarial:
             if adv_done is not None:
@@ -528,13 +505,7 @@ class VAETrainer:
         """Validation forward as the reference does it (``validate``: SAMPLED forward under no_grad,
         train_vae.py:555-560; adversarial terms :564-571; AR-VAE term :573-589).  Returns device scalars {"recon",
         "kl"[, "ar", ...][, "adv_gen", "adv_disc"]} and the reconstruction."""
-        mu, sigma, _ = self.eng.encode_forward(images, save=False)
-        eps = torch.randn(sigma.shape, generator=self.gen, device=sigma.device, dtype=sigma.dtype)
-        recon, _ = self.eng.decode_forward(torch.addcmul(mu, eps, sigma), save=False)
-        third = sigma if self.net.third_output == "sigma" else 2.0 * torch.log(sigma)
-        out2 = torch.zeros(2, dtype=torch.float32, device=recon.device)
-        ops.vae_loss(recon, images.contiguous().float(), mu, third, out2, None, None, None, l2=self.l2,
-                     third_mode=self.third_mode, kl_weight=self.kl_weight)
+        out2, recon, mu = self._forward_loss(images, None, train=False)[:3]
         res = {"recon": out2[0], "kl": out2[1]}
         if self.ar is not None:
             res["ar"], res["ar_per_attr"], res["ar_pairs"] = self._ar_term(mu, attributes, None)

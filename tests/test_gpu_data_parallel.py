@@ -112,7 +112,7 @@ def test_rccl_backend_exchange_single_rank(dev, rccl_job):
 
 
 def test_graph_step_mode_under_data_parallelism(dev, dp_job):
-    """HIP-graph step mode for world > 1 (``VAETrainer._step_graphed_dp``): [forward + loss + decoder
+    """HIP-graph step mode for world > 1 (``VAETrainer._step_graphed``): [forward + loss + decoder
     backward] and [encoder backward] are two captured graphs, the bucketed all-reduce of each region is launched eagerly
     after the graph that completes it (the decoder region's exchange runs under the second graph), Adam stays eager.
     Two ranks on the one GPU over gloo: the third step of a graph-mode trainer against the third step of an eager trainer
