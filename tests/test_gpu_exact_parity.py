@@ -9,11 +9,13 @@ behind PTI_CONV_WS=1, fused statistics, residual, pooled store, fp16 storage and
 prologue, ``ops.pool2x2_sum``, ``ops.gn_stats``, ``ops.conv_wgrad_mfma`` on every default route (route asserted, second
 launch with accumulate=True), ``ops.conv_wgrad_mfma_batched``, ``ops.wgrad_direct``.  Outputs are pre-filled with NaN.
 
-NOT covered, because their arithmetic cannot be made exact (rsqrt, exp, division): the GroupNorm(+SiLU) prologue launches,
-the fused GroupNorm-backward and chained data gradients, attention, the losses and Adam.  Their tolerance tests
-(tests/test_gpu_ops.py, test_gpu_ops2.py, test_gpu_fused_gnbwd.py, test_gpu_gnbwd_chain.py, test_gpu_attention.py, ...)
-stay as they are.  Only knobs that existing tests toggle per launch are touched: PTI_CONV_WS, PTI_CONV_WS_MAX_WGS,
-PTI_WGRAD_V6.
+The kernels that consume GroupNorm statistics -- the GroupNorm prologue launches of the convs and weight gradients,
+``gn_bwd`` / ``gn_bwd_apply``, the fused GroupNorm-backward epilogue of the data-gradient conv and the chained launch -- are
+compared exactly in tests/test_gpu_exact_groupnorm.py (a hand-written statistics table makes mean an integer and rstd a
+power of two).  What genuinely remains under tolerance only: SiLU at a non-zero argument (exp, division), the attention
+softmax, the losses and Adam (tests/test_gpu_ops.py, test_gpu_ops2.py, test_gpu_fused_gnbwd.py, test_gpu_gnbwd_chain.py,
+test_gpu_attention.py, ... stay as they are).  Only knobs that existing tests toggle per launch are touched: PTI_CONV_WS,
+PTI_CONV_WS_MAX_WGS, PTI_WGRAD_V6.
 """
 import pytest
 import torch
