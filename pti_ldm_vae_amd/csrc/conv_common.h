@@ -1,5 +1,5 @@
-// Shared by conv_mfma.hip (v1 / v2 kernels, dispatch, weight packing) and conv_ws.hip (weight-stationary persistent
-// kernel for the 128 -> 128 3x3 layers): launch arguments, the MFMA wrapper, the half-wave fold, the v2 tile geometry.
+// Included by conv_mfma.hip (v1 / v2 kernels, dispatch, weight packing): launch arguments, the MFMA wrapper, the
+// half-wave fold, the v2 tile geometry.
 #pragma once
 #include "pti_common.h"
 
@@ -125,10 +125,5 @@ struct Cfg2 {
   static constexpr int GT_OFF = GT_IN_TAIL ? EPI_BYTES : BIAS_OFF + 4 * CT;
   static constexpr int LDS_BYTES = BIAS_OFF + 4 * CT + (GT_IN_TAIL ? 0 : 8 * CT);
 };
-
-
-// conv_ws.hip: weight-stationary persistent kernel, Cin = Cout = 128, 3x3, stride-1 gathers.  Returns 0 when it took the
-// launch, 1 when the launch is not one it covers (the caller falls back to the v2 kernel), > 1 on refusal codes of launch2.
-int launch_conv_ws128(const ConvArgs& a, hipStream_t st);
 
 }  // namespace pti_conv

@@ -1183,11 +1183,7 @@ static int conv2d_mfma_impl(const void* x, const void* w_packed, const float* bi
     rc = launch_ck<3, 2>(a, ck, cout_tile, (hipStream_t)s);
   } else {
     ck = pick_ck2(d->cin, cout_tile);
-    // 128 -> 128 3x3: the weight-stationary persistent kernel (conv_ws.hip) takes the launches it covers (rc 1 = not one
-    // of them: the v2 kernel below)
-    rc = (d->ksize == 3 && d->cin == 128 && d->cout == 128 && !a.x2) ? launch_conv_ws128(a, (hipStream_t)s) : 1;
-    if (rc == 1)
-      rc = d->ksize == 1 ? launch2<1>(a, ck, cout_tile, (hipStream_t)s) : launch2<3>(a, ck, cout_tile, (hipStream_t)s);
+    rc = d->ksize == 1 ? launch2<1>(a, ck, cout_tile, (hipStream_t)s) : launch2<3>(a, ck, cout_tile, (hipStream_t)s);
   }
   if (rc == 3) PTI_FAIL(PTI_EUNSUPPORTED, "conv2d_mfma: relu_out needs a plain fp16 forward launch (w_f16, fp16 in/out, no prologue, no side output)");
   if (rc == 2) PTI_FAIL(PTI_EUNSUPPORTED, "conv2d_mfma: no fp16-operand kernel for this launch (w_f16 with this prologue / epilogue)");

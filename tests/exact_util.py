@@ -32,23 +32,23 @@ F64 = torch.float64
 
 # ---- the case tables shared by the CPU and the GPU file --------------------------------------------------------------
 def _fwd(n, cin, cout, h, w, ks, mode, seed=0, **kw):
-    d = dict(n=n, cin=cin, cout=cout, h=h, w=w, ks=ks, mode=mode, seed=seed, residual=False, pooled=False, ws=False,
+    d = dict(n=n, cin=cin, cout=cout, h=h, w=w, ks=ks, mode=mode, seed=seed, residual=False, pooled=False, nostats=False,
              f16=False, wdens=0.25, xmax=2)
     d.update(kw)
     d["id"] = (f"{mode}-k{ks}-{n}x{cin}to{cout}@{h}x{w}" + ("-pool" if d["pooled"] else "") + ("-f16" if d["f16"] else ""))
     return d
 
 
-# ``residual``: the case also runs with bias + residual (+ fused statistics where the mode has them); ``ws``: 128 -> 128,
-# also through the weight-stationary kernel; ``wdens``: P(weight != 0) (1/4 = P(+-1) = 1/8 each unless a row says why not);
-# ``xmax``: activations are uniform integers in [-xmax, xmax].
+# ``residual``: the case also runs with bias + residual (+ fused statistics where the mode has them); ``nostats``: the
+# case runs with bias + residual a second time, without the fused statistics; ``wdens``: P(weight != 0) (1/4 = P(+-1) =
+# 1/8 each unless a row says why not); ``xmax``: activations are uniform integers in [-xmax, xmax].
 FWD_CASES = [
     _fwd(2, 32, 32, 13, 19, 3, "s1", residual=True),
     _fwd(1, 64, 32, 9, 13, 3, "s1", residual=True),
     _fwd(2, 128, 64, 13, 19, 3, "s1", residual=True),
-    _fwd(2, 128, 128, 13, 19, 3, "s1", residual=True, ws=True),
+    _fwd(2, 128, 128, 13, 19, 3, "s1", residual=True, nostats=True),
     _fwd(1, 256, 256, 13, 19, 3, "s1", residual=True),            # two cin chunks, two cout tiles
-    _fwd(3, 128, 128, 24, 40, 3, "s1", residual=True, ws=True),   # 27 tiles: the tile walk
+    _fwd(3, 128, 128, 24, 40, 3, "s1", residual=True, nostats=True),  # 27 tiles: the tile walk
     # 1x1 on 32 channels: 32 terms of variance 1/2 leave 10 % zeros at P(+-1) = 1/8; 1/4 each brings that to 7 %
     _fwd(2, 32, 64, 13, 19, 1, "s1", wdens=0.5),
     _fwd(2, 128, 384, 9, 13, 1, "s1"),
@@ -58,17 +58,17 @@ FWD_CASES = [
     _fwd(2, 128, 128, 18, 26, 3, "s2"),
     _fwd(1, 256, 256, 10, 34, 3, "s2"),
     _fwd(2, 64, 64, 9, 13, 3, "up"),
-    _fwd(2, 128, 128, 9, 13, 3, "up", ws=True),
+    _fwd(2, 128, 128, 9, 13, 3, "up", nostats=True),
     _fwd(1, 256, 256, 5, 9, 3, "up"),
     _fwd(2, 32, 64, 9, 13, 3, "zins"),
-    _fwd(2, 128, 128, 9, 13, 3, "zins", ws=True),
+    _fwd(2, 128, 128, 9, 13, 3, "zins"),
     _fwd(1, 256, 256, 5, 9, 3, "zins"),
     # pooled store: four outputs are summed, so the activations are narrower ([-1, 1]) to keep the sum <= 256
     _fwd(1, 128, 64, 10, 6, 3, "s1", pooled=True, xmax=1),
     _fwd(2, 64, 64, 12, 20, 3, "s1", pooled=True, xmax=1),
     # fp16 storage and fp16 MFMA operands
     _fwd(2, 64, 64, 13, 19, 3, "s1", residual=True, f16=True),
-    _fwd(2, 128, 128, 9, 13, 3, "up", f16=True, ws=True),
+    _fwd(2, 128, 128, 9, 13, 3, "up", f16=True),
 ]
 
 # name: n, cin, cout, h, w, ksize, mode, the partial kernel the default rules pick (spelled as

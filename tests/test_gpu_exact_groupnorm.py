@@ -9,7 +9,7 @@ tests/test_exact_gn_util_cpu.py.
 
 The probe (``test_probe_*``).  All of this rests on the reciprocal square root being EXACT on powers of four, which each
 kernel family computes in its own way (``rsqrtf`` in groupnorm.hip, the stride-2 conv kernel, the chained loader and the
-weight gradients; ``__builtin_amdgcn_rsqf`` in ``gn_params``: the v2 / weight-stationary conv kernels and the fused
+weight gradients; ``__builtin_amdgcn_rsqf`` in ``gn_params``: the v2 conv kernel and the fused
 epilogue; conv_direct.hip its own).  One tiny launch per family with x = 1, mean = 0, gamma = 1, beta = 0 and an identity
 tap returns rstd itself, for var + eps in {1/4, 1, 4, 16}.  Measured on an MI355X (gfx950):
 
@@ -18,7 +18,6 @@ tap returns rstd itself, for var + eps in {1/4, 1, 4, 16}.  Measured on an MI355
     gn_bwd_apply (rsqrtf)                                                    2      1    1/2   1/4
     conv_mfma_v2 (conv_mfma2_kernel, gn_params: v_rsq_f32)                   2      1    1/2   1/4
     conv_mfma_s2 (conv_mfma_kernel, stride 2, rsqrtf)                        2      1    1/2   1/4
-    conv_ws (conv_ws128_kernel, PTI_CONV_WS=1)                               2      1    1/2   1/4
     conv_direct prologue                                                     2      1    1/2   1/4
     wgrad_direct prologue                                                    2      1    1/2   1/4
     conv_wgrad_mfma prologue, 3x3 (wgrad_mfma3_kernel)                       2      1    1/2   1/4
@@ -87,7 +86,7 @@ def _single(name, t):
     return v[0].item()
 
 
-def _probe_conv(ops, dev, eps, *, c, mode, ks=3, f16=False, ws=False, monkeypatch=None):
+def _probe_conv(ops, dev, eps, *, c, mode, ks=3, f16=False):
     n, h, w = 1, 8, 16
     sdt = H16 if f16 else B16
     m = _mode(ops, mode)
@@ -95,16 +94,14 @@ def _probe_conv(ops, dev, eps, *, c, mode, ks=3, f16=False, ws=False, monkeypatc
     wp = ops.pack_conv_weight(_identity(c, c, ks, dev), ks, m, f16=f16)
     ho, wo = ops.conv_out_hw(h, w, m)
     y = _nan((n, ho, wo, c), sdt, dev)
-    monkeypatch.setenv("PTI_CONV_WS", "1" if ws else "0")
     ops.conv_mfma(x, wp, None, y, cout=c, ksize=ks, mode=m, prologue=ops.PTI_PRO_GN,
                   in_stats=torch.zeros(n, 16, 2, dtype=torch.int64, device=dev), gamma=torch.ones(c, device=dev),
                   beta=torch.zeros(c, device=dev), groups=16, eps=eps)
     torch.cuda.synchronize()
-    monkeypatch.delenv("PTI_CONV_WS", raising=False)
     return _single("conv_mfma", y), ops.last_kernel_name()
 
 
-def _probe_family(ops, dev, family, eps, monkeypatch):
+def _probe_family(ops, dev, family, eps):
     """-> the rstd the family computes for var + eps = ``eps`` (an all-zero table: mean 0, var 0)."""
     z = lambda n, g=16: torch.zeros(n, g, 2, dtype=torch.int64, device=dev)
     ones = lambda c: torch.ones(c, device=dev)
@@ -123,16 +120,12 @@ def _probe_family(ops, dev, family, eps, monkeypatch):
         torch.cuda.synchronize()
         return _single(family, dx.float() * dy.float())
     if family == "conv_mfma_v2":
-        v, name = _probe_conv(ops, dev, eps, c=32, mode="s1", monkeypatch=monkeypatch)
+        v, name = _probe_conv(ops, dev, eps, c=32, mode="s1")
         assert name.startswith("conv_mfma2_kernel<"), name
         return v
     if family == "conv_mfma_s2":
-        v, name = _probe_conv(ops, dev, eps, c=32, mode="s2", monkeypatch=monkeypatch)
+        v, name = _probe_conv(ops, dev, eps, c=32, mode="s2")
         assert name.startswith("conv_mfma_kernel<"), name
-        return v
-    if family == "conv_ws":
-        v, name = _probe_conv(ops, dev, eps, c=128, mode="s1", f16=True, ws=True, monkeypatch=monkeypatch)
-        assert name.startswith("conv_ws128_kernel<"), name
         return v
     if family == "conv_direct":
         n, h, w, cin, cout = 1, 8, 8, 32, 1
@@ -186,15 +179,15 @@ def _probe_family(ops, dev, family, eps, monkeypatch):
 
 
 PROBE_FAMILIES = {"gn_bwd": "gn_bwd", "gn_bwd_apply": "gn_bwd_apply", "conv_mfma_v2": "conv_mfma_v2",
-                  "conv_mfma_s2": "conv_mfma_s2", "conv_ws": "conv_ws", "conv_direct": "conv_direct",
+                  "conv_mfma_s2": "conv_mfma_s2", "conv_direct": "conv_direct",
                   "wgrad_direct": "wgrad_direct", "conv_wgrad_mfma": "conv_wgrad_mfma", "conv_wgrad_mfma_1x1": "conv_wgrad_mfma",
                   "conv_mfma_gnbwd": "conv_mfma_gnbwd", "chain": "chain"}
 
 
 @pytest.mark.parametrize("family", list(PROBE_FAMILIES))
-def test_probe_rstd_is_exact_on_powers_of_four(dev, monkeypatch, family):
+def test_probe_rstd_is_exact_on_powers_of_four(dev, family):
     from pti_ldm_vae_amd import ops
-    got = {ve: _probe_family(ops, dev, family, ve, monkeypatch) for ve in PROBE_VE}
+    got = {ve: _probe_family(ops, dev, family, ve) for ve in PROBE_VE}
     exact = tuple(ve ** -0.5 for ve in PROBE_VE if got[ve] == ve ** -0.5)
     print(f"[probe] {family}: " + ", ".join(f"var+eps={ve:g} -> {got[ve]!r}" for ve in PROBE_VE) + f"; exact: {exact}")
     assert 1.0 in exact, f"{family}: rstd(1) = {got[1.0]!r}: this family has to stay under its tolerance tests"
@@ -229,7 +222,7 @@ def _prologue_args(ops, s, dev):
 
 
 @pytest.mark.parametrize("row", PRO, ids=[r["id"] for r in PRO])
-def test_conv_mfma_prologue_exact(dev, monkeypatch, row):
+def test_conv_mfma_prologue_exact(dev, row):
     from pti_ldm_vae_amd import ops
     c = _cached(("pro", row["id"]), lambda: X.make_prologue_case(row))
     s, n, cin, cout, ks = c.s, row["n"], row["cin"], row["cout"], row["ks"]
@@ -238,33 +231,26 @@ def test_conv_mfma_prologue_exact(dev, monkeypatch, row):
     wp = ops.pack_conv_weight(_f32(c.w, dev), ks, m, f16=row["f16"])
     xd, resd = _nhwc(c.x, dev, sdt), _nhwc(c.res, dev, sdt)
     ho, wo = ops.conv_out_hw(row["h"], row["w"], m)
-    kernels = [("0", "conv_mfma_kernel<" if row["mode"] == "s2" else "conv_mfma2_kernel<")]
-    if row["f16"] and cin == cout == 128 and ks == 3 and row["mode"] in ("s1", "up"):
-        kernels.append(("1", "conv_ws128_kernel<"))       # the weight-stationary kernel takes fp16 GroupNorm launches
+    want = "conv_mfma_kernel<" if row["mode"] == "s2" else "conv_mfma2_kernel<"
     # (reference, bias, residual, fused statistics, act_out)
     variants = [("plain", False, False, False, False), ("full", True, True, row["stats"], False)]
     if ks == 3 and row["mode"] == "s1" and (not row["f16"] or cout <= 64):
         variants.append(("bias", True, False, False, True))
-    for ws, want in kernels:
-        monkeypatch.setenv("PTI_CONV_WS", ws)
-        for name, bias, res, stats, act in variants:
-            if act and ws == "1":
-                continue
-            tag = f"conv_mfma GN prologue [{row['id']}] {name} stats={stats} act_out={act} ws={ws}"
-            y = _nan((n, ho, wo, cout), sdt, dev)
-            ost = torch.zeros(n, E.STATS_GROUPS, 2, dtype=torch.int64, device=dev) if stats else None
-            actd = _nan(xd.shape, B16, dev) if act else None
-            ops.conv_mfma(xd, wp, _f32(c.bias, dev) if bias else None, y, cout=cout, ksize=ks, mode=m, residual=resd if res else None,
-                          out_stats=ost, out_groups=E.STATS_GROUPS if stats else 0, act_out=actd, **_prologue_args(ops, s, dev))
-            torch.cuda.synchronize()
-            got = ops.last_kernel_name()
-            assert got.startswith(want), f"{tag}: went down {got}"
-            E.assert_exact(tag, y, c.ref[name, sdt], layout="nhwc")
-            if stats:
-                E.assert_exact(tag + " fused statistics", ost, c.ref[name + "_stats", sdt], layout="flat")
-            if act:
-                E.assert_exact(tag + " act_out", actd, c.a, layout="nhwc")
-    monkeypatch.delenv("PTI_CONV_WS", raising=False)
+    for name, bias, res, stats, act in variants:
+        tag = f"conv_mfma GN prologue [{row['id']}] {name} stats={stats} act_out={act}"
+        y = _nan((n, ho, wo, cout), sdt, dev)
+        ost = torch.zeros(n, E.STATS_GROUPS, 2, dtype=torch.int64, device=dev) if stats else None
+        actd = _nan(xd.shape, B16, dev) if act else None
+        ops.conv_mfma(xd, wp, _f32(c.bias, dev) if bias else None, y, cout=cout, ksize=ks, mode=m, residual=resd if res else None,
+                      out_stats=ost, out_groups=E.STATS_GROUPS if stats else 0, act_out=actd, **_prologue_args(ops, s, dev))
+        torch.cuda.synchronize()
+        got = ops.last_kernel_name()
+        assert got.startswith(want), f"{tag}: went down {got}"
+        E.assert_exact(tag, y, c.ref[name, sdt], layout="nhwc")
+        if stats:
+            E.assert_exact(tag + " fused statistics", ost, c.ref[name + "_stats", sdt], layout="flat")
+        if act:
+            E.assert_exact(tag + " act_out", actd, c.a, layout="nhwc")
     if row["f16"]:
         # fp16 storage with bf16-packed weights: the loader converts the staged operand to bf16 (the run-time-format kernel)
         tag = f"conv_mfma GN prologue [{row['id']}] full, bf16-packed weights"
@@ -273,7 +259,7 @@ def test_conv_mfma_prologue_exact(dev, monkeypatch, row):
         ops.conv_mfma(xd, ops.pack_conv_weight(_f32(c.w, dev), ks, m), _f32(c.bias, dev), y, cout=cout, ksize=ks, mode=m,
                       residual=resd, out_stats=ost, out_groups=E.STATS_GROUPS if row["stats"] else 0, **_prologue_args(ops, s, dev))
         torch.cuda.synchronize()
-        assert ops.last_kernel_name().startswith(kernels[0][1]), f"{tag}: went down {ops.last_kernel_name()}"
+        assert ops.last_kernel_name().startswith(want), f"{tag}: went down {ops.last_kernel_name()}"
         E.assert_exact(tag, y, c.ref["full", sdt], layout="nhwc")
         if row["stats"]:
             E.assert_exact(tag + " fused statistics", ost, c.ref["full_stats", sdt], layout="flat")
@@ -417,29 +403,23 @@ def _fused_launch(ops, dev, c, row, x16, silu):
 
 @pytest.mark.parametrize("x16", [B16, H16], ids=["bf16", "fp16"])
 @pytest.mark.parametrize("row", FUSED, ids=[r["id"] for r in FUSED])
-def test_conv_mfma_gnbwd_exact(dev, monkeypatch, row, x16):
+def test_conv_mfma_gnbwd_exact(dev, row, x16):
     from pti_ldm_vae_amd import ops
     c = _cached(("fused", row["id"]), lambda: X.make_fused_case(row))
     s, ch = c.s, row["cin"]
-    routes = [("0", "conv_mfma2_kernel<")]
-    if x16 == H16 and row["cin"] == row["cout"] == 128 and row["ks"] == 3:
-        routes.append(("1", "conv_ws128_kernel<"))
-    for ws, want in routes:
-        monkeypatch.setenv("PTI_CONV_WS", ws)
-        tag = f"conv_mfma_gnbwd [{row['id']}] ws={ws}"
-        dy_out, gsums, name = _fused_launch(ops, dev, c, row, x16, False)
-        assert name.startswith(want), f"{tag}: went down {name}"
-        E.assert_exact(tag + " dy_out", dy_out, c.g, layout="nhwc")
-        E.assert_exact(tag + " gsums", gsums, c.ref.sums, layout="flat")
-        xd = _nhwc(c.gx, dev, x16)
-        dx, dg, db = _nan(xd.shape, B16, dev), torch.zeros(ch, device=dev), torch.zeros(ch, device=dev)
-        ops.gn_bwd_apply(xd, dy_out, dx, s.stats.to(dev), _f32(s.gamma, dev), _f32(s.beta, dev), gsums, dg, db, groups=s.groups,
-                         eps=s.eps, dres=_nhwc(c.dres, dev, B16))
-        torch.cuda.synchronize()
-        E.assert_exact(tag + " -> gn_bwd_apply dx", dx, c.ref_res.dx16, layout="nhwc")
-        E.assert_exact(tag + " -> gn_bwd_apply dgamma", dg, c.ref.dgamma, layout="flat")
-        E.assert_exact(tag + " -> gn_bwd_apply dbeta", db, c.ref.dbeta, layout="flat")
-    monkeypatch.delenv("PTI_CONV_WS", raising=False)
+    tag = f"conv_mfma_gnbwd [{row['id']}]"
+    dy_out, gsums, name = _fused_launch(ops, dev, c, row, x16, False)
+    assert name.startswith("conv_mfma2_kernel<"), f"{tag}: went down {name}"
+    E.assert_exact(tag + " dy_out", dy_out, c.g, layout="nhwc")
+    E.assert_exact(tag + " gsums", gsums, c.ref.sums, layout="flat")
+    xd = _nhwc(c.gx, dev, x16)
+    dx, dg, db = _nan(xd.shape, B16, dev), torch.zeros(ch, device=dev), torch.zeros(ch, device=dev)
+    ops.gn_bwd_apply(xd, dy_out, dx, s.stats.to(dev), _f32(s.gamma, dev), _f32(s.beta, dev), gsums, dg, db, groups=s.groups,
+                     eps=s.eps, dres=_nhwc(c.dres, dev, B16))
+    torch.cuda.synchronize()
+    E.assert_exact(tag + " -> gn_bwd_apply dx", dx, c.ref_res.dx16, layout="nhwc")
+    E.assert_exact(tag + " -> gn_bwd_apply dgamma", dg, c.ref.dgamma, layout="flat")
+    E.assert_exact(tag + " -> gn_bwd_apply dbeta", db, c.ref.dbeta, layout="flat")
 
 
 @pytest.mark.parametrize("row", FUSED[:1] + FUSED[2:4], ids=[r["id"] for r in FUSED[:1] + FUSED[2:4]])

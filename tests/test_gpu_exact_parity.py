@@ -4,9 +4,8 @@ every 16-bit store within |v| <= 256, so nothing rounds and kernel == reference,
 indexing, masking or staging bug; ``assert_exact`` names its tile position and channel block.  The conditions are asserted
 when a case is built, and tests/test_exact_util_cpu.py builds every case of this file on the CPU.
 
-Covered: ``ops.conv_mfma`` forward and data gradient (v2 kernel, stride-2 kernel, the weight-stationary 128 -> 128 kernel
-behind PTI_CONV_WS=1, fused statistics, residual, pooled store, fp16 storage and operands), ``ops.conv_direct`` without
-prologue, ``ops.pool2x2_sum``, ``ops.gn_stats``, ``ops.conv_wgrad_mfma`` on every default route (route asserted, second
+Covered: ``ops.conv_mfma`` forward and data gradient (v2 kernel, stride-2 kernel, kernel name asserted, fused
+statistics, residual, pooled store, fp16 storage and operands), ``ops.conv_direct`` without prologue, ``ops.pool2x2_sum``, ``ops.gn_stats``, ``ops.conv_wgrad_mfma`` on every default route (route asserted, second
 launch with accumulate=True), ``ops.conv_wgrad_mfma_batched``, ``ops.wgrad_direct``.  Outputs are pre-filled with NaN.
 
 The kernels that consume GroupNorm statistics -- the GroupNorm prologue launches of the convs and weight gradients,
@@ -14,8 +13,8 @@ The kernels that consume GroupNorm statistics -- the GroupNorm prologue launches
 compared exactly in tests/test_gpu_exact_groupnorm.py (a hand-written statistics table makes mean an integer and rstd a
 power of two).  What genuinely remains under tolerance only: SiLU at a non-zero argument (exp, division), the attention
 softmax, the losses and Adam (tests/test_gpu_ops.py, test_gpu_ops2.py, test_gpu_fused_gnbwd.py, test_gpu_gnbwd_chain.py,
-test_gpu_attention.py, ... stay as they are).  Only knobs that existing tests toggle per launch are touched: PTI_CONV_WS,
-PTI_CONV_WS_MAX_WGS, PTI_WGRAD_V6.
+test_gpu_attention.py, ... stay as they are).  The only knob touched is one that existing tests toggle per launch:
+PTI_WGRAD_V6.
 """
 import pytest
 import torch
@@ -61,48 +60,34 @@ def _conv(ops, dev, row, c, wp, xd, sdt, *, bias, residual, stats, pool=False):
 def _variants(row):
     """(bias, residual, fused statistics) of each launch of a case: always the bare conv; then bias plus what the mode's
     launches carry in the product (and in the tolerance tests): statistics on the 3x3 forward modes, the residual where the
-    case table asks for it.  The weight-stationary kernel takes no bf16 launch with statistics, so its bf16 rows also run
-    with bias and residual alone."""
+    case table asks for it.  The ``nostats`` rows also run with bias and residual alone."""
     if row["pooled"]:
         return [(False, False, False)]
     stats = row["ks"] == 3 and row["mode"] in ("s1", "s2", "up")
     out = [(False, False, False), (True, row["residual"], stats)]
-    if row["ws"] and stats and not row["f16"]:
+    if row["nostats"]:
         out.append((True, row["residual"], False))
     return out
 
 
 @pytest.mark.parametrize("row", E.FWD_CASES, ids=[r["id"] for r in E.FWD_CASES])
-def test_conv_mfma_exact(dev, monkeypatch, row):
+def test_conv_mfma_exact(dev, row):
     from pti_ldm_vae_amd import ops
     c = _cached(("fwd", row["id"]), lambda: E.make_fwd_case(row))
     sdt = H16 if row["f16"] else B16
     m = _mode(ops, row["mode"])
     wp = ops.pack_conv_weight(c.w.to(dev, F32), row["ks"], m, flip=row["mode"] == "zins", f16=row["f16"])
     xd = _nhwc(c.x, dev, sdt)
-    expect = "conv_mfma_kernel<" if row["mode"] == "s2" else "conv_mfma2_kernel<"
-    kernels = [("0", None, expect)]
-    if row["ws"]:          # the grid cap makes every persistent workgroup walk several tiles
-        kernels += [("1", None, "conv_ws128_kernel<"), ("1", "5", "conv_ws128_kernel<")]
-    for ws, cap, want in kernels:
-        monkeypatch.setenv("PTI_CONV_WS", ws)
-        if cap:
-            monkeypatch.setenv("PTI_CONV_WS_MAX_WGS", cap)
-        else:
-            monkeypatch.delenv("PTI_CONV_WS_MAX_WGS", raising=False)
-        for bias, residual, stats in _variants(row):
-            # the weight-stationary kernel leaves bf16 launches with fused statistics to the v2 kernel
-            declined = want.startswith("conv_ws128") and stats and not row["f16"]
-            tag = f"conv_mfma[{row['id']}] bias={bias} res={residual} stats={stats} ws={ws} cap={cap}"
-            y, ost, name = _conv(ops, dev, row, c, wp, xd, sdt, bias=bias, residual=residual, stats=stats, pool=row["pooled"])
-            assert name.startswith("conv_mfma2_kernel<" if declined else want), f"{tag}: went down {name}"
-            ref = c.pool if row["pooled"] else c.ref_full if residual else c.ref_bias if bias else c.conv
-            E.assert_exact(tag, y, ref, layout="nhwc", tile=(4, 8) if row["pooled"] else E.TILE)
-            if stats:      # Q47.16 sums of integers: the int64 sums of the reference, shifted
-                E.assert_exact(tag + " fused statistics", ost, (c.stats_full if residual else c.stats_bias) * E.STAT_SCALE,
-                               layout="flat")
-    monkeypatch.delenv("PTI_CONV_WS", raising=False)
-    monkeypatch.delenv("PTI_CONV_WS_MAX_WGS", raising=False)
+    want = "conv_mfma_kernel<" if row["mode"] == "s2" else "conv_mfma2_kernel<"
+    for bias, residual, stats in _variants(row):
+        tag = f"conv_mfma[{row['id']}] bias={bias} res={residual} stats={stats}"
+        y, ost, name = _conv(ops, dev, row, c, wp, xd, sdt, bias=bias, residual=residual, stats=stats, pool=row["pooled"])
+        assert name.startswith(want), f"{tag}: went down {name}"
+        ref = c.pool if row["pooled"] else c.ref_full if residual else c.ref_bias if bias else c.conv
+        E.assert_exact(tag, y, ref, layout="nhwc", tile=(4, 8) if row["pooled"] else E.TILE)
+        if stats:      # Q47.16 sums of integers: the int64 sums of the reference, shifted
+            E.assert_exact(tag + " fused statistics", ost, (c.stats_full if residual else c.stats_bias) * E.STAT_SCALE,
+                           layout="flat")
 
 
 # ---- the degenerate-channel conv ---------------------------------------------------------------------------------------
