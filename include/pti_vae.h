@@ -52,7 +52,9 @@ typedef void* pti_stream_t; /* hipStream_t */
                                Still 5: pti_ssim_uniform (+ its _ws_bytes) / pti_mask_compare_cleaned appended in the same
                                way.
                                Still 5: pti_mask_compare_outputs / pti_surface_distance (+ its _ws_bytes) appended in the same
-                               way. */
+                               way.
+                               Still 5: pti_distance_median / pti_permutation_forms (+ their _ws_bytes) / pti_two_sample_kernel /
+                               pti_knn_indicator appended in the same way. */
 
 #define PTI_OK 0
 #define PTI_EINVAL (-1)   /* bad pointer / dimension */
@@ -1042,6 +1044,43 @@ int64_t pti_surface_distance_ws_bytes(int n, int h, int w);
 int pti_surface_distance(const uint8_t* a, int a_bits, const uint8_t* b, int b_bits, int n, int h, int w, int percentile_pm,
                          const int32_t* tol_d2, int n_tol, int32_t* counts, double* sums, void* workspace, int64_t ws_bytes,
                          pti_stream_t s);
+
+/* ---- two-sample permutation tests of two groups of latent rows (unbiased MMD^2, energy distance, Schilling-Henze
+ *      nearest-neighbour share; csrc/two_sample.hip) ----
+ * 4 <= n <= 8192 everywhere; dist: fp32 [n][n] of non-negative distances, row stride ldd >= n in ELEMENTS, used in place.
+ * pti_distance_median: out (one DEVICE float) = the exact lower median of the M = n (n - 1) / 2 entries above the diagonal,
+ *   element (M - 1) / 2 in ascending order, by an MSB-first radix select over the entries' bit patterns (-0 taken as 0):
+ *   integer histograms only, no sort, no copy of the triangle, no host synchronisation.
+ *   workspace: pti_distance_median_ws_bytes(n) bytes, 4-byte aligned (0 = unsupported n); cleared by the call.
+ * pti_two_sample_kernel: out int32 [n][n] dense, entries in [0, 65535], zero diagonal.  With s = the scale,
+ *     kind 0 (gaussian): out = rint(65535 * mean_b exp(-d^2 / (2 (bandwidths[b] s)^2))),  s = *scale (a DEVICE float, required)
+ *     kind 1 (energy):   out = rint(65535 * d / s),  s = *scale, or with scale null the maximum entry of dist, found on the
+ *                        device by an integer maximum over the bit patterns
+ *   evaluated in fp64 from the fp32 distance and rounded once.  A scale that is not positive gives an all-zero matrix.
+ *   bandwidths: HOST array of 1 .. 8 positive values, read before the call returns (kind 0 only).  scale_out: one DEVICE
+ *   float that receives the scale used; it may be the scale pointer itself.
+ * pti_knn_indicator: knn_idx int32 [n][k] dense, 1 <= k <= n.  out int32 [n][n] dense: out[i][j] = 1 where j is listed in
+ *   row i of knn_idx and j != i, else 0.  An index outside [0, n) is skipped, never dereferenced.
+ * pti_permutation_forms: w int32 [n][n] with entries in [0, 65535] (only the low 16 bits of an entry are used), row stride
+ *   ldw >= n in ELEMENTS; it need not be symmetric.  masks uint8 [p][n] dense, any value but 0 taken as 1; 1 <= p <= 65536.
+ *   out int64 [p][3] = { s^T W s,  s . (W 1),  s . (W^T 1) } for every row s of masks.  W is split into two int8 byte planes
+ *   and T = S . plane runs on v_mfma_i32_16x16x64_i8 with i32 accumulators (|sum| <= 2^20); the planes, the labellings and
+ *   the tiles are combined in 64-bit integers.  Every output integer is exact, independent of tiling and launch order, and
+ *   bitwise reproducible.
+ *   workspace: pti_permutation_forms_ws_bytes(n, p) bytes (two planes of n_pad^2 bytes, p n_pad bytes of labellings, 8 n
+ *   bytes of sums, n_pad = n rounded up to 64), 16-byte aligned, ws_bytes = its size (pure host arithmetic; 0 = unsupported
+ *   shape); every byte read is written earlier in the same call.
+ * All on the caller's stream without a host synchronisation.  Refused before any launch: null pointers, n < 4, p < 1, k
+ * outside 1 .. n, a kind other than 0 / 1, a bandwidth count outside 1 .. 8 or a bandwidth that is not positive, a row stride
+ * below the row length, a misaligned buffer, a short workspace (PTI_EINVAL); n > 8192, p > 65536 (PTI_EUNSUPPORTED).          */
+int64_t pti_distance_median_ws_bytes(int n);
+int pti_distance_median(const float* dist, int64_t ldd, int n, float* out, void* workspace, int64_t ws_bytes, pti_stream_t s);
+int pti_two_sample_kernel(const float* dist, int64_t ldd, int n, int kind, const float* scale_or_null, const double* bandwidths,
+                          int n_bandwidths, int32_t* out, float* scale_out, pti_stream_t s);
+int pti_knn_indicator(const int32_t* knn_idx, int n, int k, int32_t* out, pti_stream_t s);
+int64_t pti_permutation_forms_ws_bytes(int n, int p);
+int pti_permutation_forms(const int32_t* w, int64_t ldw, int n, const uint8_t* masks, int p, int64_t* out, void* workspace,
+                          int64_t ws_bytes, pti_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -227,6 +227,12 @@ SIGNATURES = {
     "pti_mask_compare_outputs": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I64, _P]),
     "pti_surface_distance_ws_bytes": (_I64, [_I, _I, _I]),
     "pti_surface_distance": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _P, _P, _P, _I64, _P]),
+    "pti_distance_median_ws_bytes": (_I64, [_I]),
+    "pti_distance_median": (_I, [_P, _I64, _I, _P, _P, _I64, _P]),
+    "pti_two_sample_kernel": (_I, [_P, _I64, _I, _I, _P, C.POINTER(_D), _I, _P, _P, _P]),
+    "pti_knn_indicator": (_I, [_P, _I, _I, _P, _P]),
+    "pti_permutation_forms_ws_bytes": (_I64, [_I, _I]),
+    "pti_permutation_forms": (_I, [_P, _I64, _I, _P, _I, _P, _P, _I64, _P]),
 }
 
 _lib = None

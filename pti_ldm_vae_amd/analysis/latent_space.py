@@ -518,6 +518,13 @@ class LatentSpaceAnalyzer:
         from .coranking import coranking_curves
         return coranking_curves(latent_vectors, projection, bins=bins, device=self.device)
 
+    def group_separation_test(self, latents_a, latents_b, **options) -> tuple[dict, dict]:
+        """Do two groups of latent rows differ by more than chance?  Permutation tests of the unbiased MMD^2, the energy
+        distance and the same-label neighbour share -> ``(report, arrays)``: ``analysis.two_sample_tests`` on this
+        analyzer's device."""
+        from .two_sample import two_sample_tests
+        return two_sample_tests(latents_a, latents_b, device=self.device, **options)
+
     # ---- colours ----
     def create_patient_colormap(self, patient_ids: list[str]) -> tuple[dict[str, int], dict[str, str]]:
         """-> (patient -> index in sorted order, patient -> hex colour, cycling through ``PATIENT_PALETTE``)."""

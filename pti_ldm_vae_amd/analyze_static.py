@@ -20,6 +20,9 @@ groups and a patient's exams are in the latent space and in the picture) into ``
 co-ranking curves Q_NX, B_NX, R_NX for every neighbourhood size, their scale-free score, the rank correlation per point and
 a Shepard diagram with its stress) into ``projection_curves.json``, ``projection_curves.npz`` and
 ``<method>_projection_curves.png``; it is independent of ``--quality``, and without it nothing changes either.
+``--group-test`` asks whether the two groups differ by more than chance (``analysis.two_sample``: permutation tests of the
+unbiased MMD^2, the energy distance and the same-label neighbour share on the latents, exact integer arithmetic on the
+device) into ``group_test.json``, ``group_test.npz`` and ``group_test.png``; without it nothing changes.
 
 Images are encoded deterministically in batches on the HIP engine; each image's latent is cached on disk in the
 reference's layout (``analysis.LatentCache``), so a second run on the same folders encodes nothing."""
@@ -36,7 +39,7 @@ from .analysis import LatentCache, LatentSpaceAnalyzer, load_image_paths
 
 class _Args(argparse.Namespace):
     """The namespace ``parse_args`` fills.  ``--tsne-backend``, ``--umap-backend``, ``--umap-fit-group``, ``--quality``,
-    ``--quality-neighbors``, ``--quality-curves`` and ``--quality-bins`` live here as class defaults and enter the instance
+    ``--quality-neighbors``, ``--quality-curves``, ``--quality-bins`` and the ``--group-test`` family live here as class defaults and enter the instance
     only when they are given, so a command line without them parses to exactly the attributes it always had."""
 
     tsne_backend = "sklearn"
@@ -46,6 +49,11 @@ class _Args(argparse.Namespace):
     quality_neighbors = (5, 15, 40)
     quality_curves = False
     quality_bins = 64
+    group_test = False
+    group_test_permutations = 9999
+    group_test_stratify = "none"
+    group_test_neighbors = 5
+    group_test_seed = 0
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -85,6 +93,18 @@ def parse_args(argv=None) -> argparse.Namespace:
                              "stress (projection_curves.json / .npz and <method>_projection_curves.png)")
     parser.add_argument("--quality-bins", type=int, default=argparse.SUPPRESS, metavar="B",
                         help="Bins per axis of the Shepard diagram of --quality-curves (default: 64; 2 .. 128)")
+    parser.add_argument("--group-test", action="store_true", default=argparse.SUPPRESS,
+                        help="Also test whether the two groups differ by more than chance: permutation tests of the unbiased "
+                             "MMD^2, the energy distance and the same-label nearest-neighbour share on the latents "
+                             "(group_test.json / .npz / .png); needs --folder-dente")
+    parser.add_argument("--group-test-permutations", type=int, default=argparse.SUPPRESS, metavar="P",
+                        help="Relabellings of --group-test (default: 9999; 1 .. 65534)")
+    parser.add_argument("--group-test-stratify", type=str, choices=["none", "patient"], default=argparse.SUPPRESS,
+                        help="Relabel freely (none; default) or only within a patient (patient)")
+    parser.add_argument("--group-test-neighbors", type=int, default=argparse.SUPPRESS, metavar="K",
+                        help="Nearest neighbours of --group-test's neighbour test (default: 5)")
+    parser.add_argument("--group-test-seed", type=int, default=argparse.SUPPRESS,
+                        help="Seed of --group-test's relabellings (default: 0)")
     parser.add_argument("--seed", type=int, default=42, help="Random seed for reproducibility")
     parser.add_argument("--subtitle", type=str, default=None, help="Optional subtitle for the plot")
     parser.add_argument("--dpi", type=int, default=300, help="DPI for output PNG (default: 300)")
@@ -335,6 +355,60 @@ def write_projection_curves(analyzer: LatentSpaceAnalyzer, groups: list, project
     return report
 
 
+def save_group_test_plot(report: dict, arrays: dict, output_path: Path, dpi: int) -> Path:
+    """One panel per test: the null histogram with the observed value marked."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    titles = {"mmd": "unbiased MMD^2", "energy": "energy distance", "knn": "same-label neighbour share"}
+    fig, axes = plt.subplots(1, 3, figsize=(18, 5))
+    for ax, (name, entry) in zip(axes, report["tests"].items()):
+        if entry["statistic"] is None:
+            ax.set_title(f"{titles[name]}: undefined")
+            continue
+        ax.hist(arrays[f"null_{name}"], bins=40, color="#7f7f7f")
+        ax.axvline(entry["statistic"], color="#d62728", label=f"observed (p = {entry['p_value']:.4g})")
+        ax.set_title(titles[name])
+        ax.set_xlabel("statistic")
+        ax.legend(loc="best")
+        ax.grid(True, color="lightgray")
+    fig.savefig(output_path, dpi=dpi)
+    plt.close(fig)
+    return output_path
+
+
+def write_group_test(analyzer: LatentSpaceAnalyzer, groups: list, args: argparse.Namespace, output_dir: Path) -> dict:
+    """``--group-test``: the permutation tests of the first group's latents against the second's ->
+    ``group_test.json`` (byte-identical between two runs), ``group_test.npz`` (null distributions, integer tables, labellings,
+    the per-image witness, ids and paths, pooled with the first group first) and ``group_test.png``.  -> the report."""
+    import json
+    (lat_a, ids_a, paths_a, name_a), (lat_b, ids_b, paths_b, name_b) = groups[0], groups[1]
+    lat_a, lat_b = (np.asarray(x).reshape(len(x), -1) for x in (lat_a, lat_b))
+    stratify = getattr(args, "group_test_stratify", _Args.group_test_stratify)
+    options = dict(permutations=int(getattr(args, "group_test_permutations", _Args.group_test_permutations)),
+                   seed=int(getattr(args, "group_test_seed", _Args.group_test_seed)),
+                   neighbors=int(getattr(args, "group_test_neighbors", _Args.group_test_neighbors)))
+    try:
+        report, arrays = analyzer.group_separation_test(lat_a, lat_b, strata_a=ids_a if stratify == "patient" else None,
+                                                        strata_b=ids_b if stratify == "patient" else None, **options)
+    except ValueError as e:
+        raise SystemExit(f"analyze_static: --group-test: {e}")
+    doc = {"group_a": name_a, "group_b": name_b, "stratify": stratify}
+    doc.update(report)
+    (output_dir / "group_test.json").write_text(json.dumps(doc, indent=2, allow_nan=False) + "\n")
+    np.savez(output_dir / "group_test.npz", ids=np.array(list(ids_a) + list(ids_b)), paths=np.array(list(paths_a) + list(paths_b)),
+             groups=np.array([name_a] * len(ids_a) + [name_b] * len(ids_b)), **arrays)
+    save_group_test_plot(report, arrays, output_dir / "group_test.png", args.dpi)
+    for name, entry in report["tests"].items():
+        if entry["statistic"] is None:
+            print(f"Group test {name}: undefined")
+        else:
+            print(f"Group test {name}: statistic {entry['statistic']:.6g}, p = {entry['p_value']:.4g} "
+                  f"({entry['exceed']} of {entry['permutations']} relabellings at least as large)")
+    print(f"✅ Group test saved: {output_dir / 'group_test.json'}")
+    return report
+
+
 def main(argv=None) -> None:
     from . import _lib
     from .utils.cli_common import init_device_and_seed, load_config_and_model
@@ -344,6 +418,8 @@ def main(argv=None) -> None:
     if fit_first and getattr(args, "umap_backend", "umap-learn") != "hip":
         raise SystemExit("analyze_static: --umap-fit-group edente places the second group with the device UMAP's transform; "
                          "add --umap-backend hip")
+    if getattr(args, "group_test", False) and not args.folder_dente:
+        raise SystemExit("analyze_static: --group-test compares two groups; add --folder-dente")
     device = init_device_and_seed(args.seed)
     np.random.seed(args.seed)
     output_dir = Path(args.output_dir)
@@ -398,6 +474,8 @@ def main(argv=None) -> None:
         write_projection_quality(analyzer, groups, projected, method, args, output_dir)
     if getattr(args, "quality_curves", False):
         write_projection_curves(analyzer, groups, projected, method, args, output_dir)
+    if getattr(args, "group_test", False):
+        write_group_test(analyzer, groups, args, output_dir)
     print("✅ Analysis complete!")
 
 

@@ -2508,3 +2508,124 @@ def augment_warp(src, mat, field=None, out=None):
     out = _out(out, src.shape, F32, src.device, "augment_warp: out", msg="augment_warp: out must have the shape and device of src")
     L.check(L.lib().pti_augment_warp(_ptr(src), _ptr(mat), _ptr(field), b, c, h, w, _ptr(out), _stream()), "pti_augment_warp")
     return out
+
+
+# ---- two-sample permutation tests (csrc/two_sample.hip; include/pti_vae.h "two-sample permutation tests") ------------------
+TWO_SAMPLE_MIN_N, TWO_SAMPLE_MAX_N, TWO_SAMPLE_MAX_P, TWO_SAMPLE_MAX_BANDWIDTHS, TWO_SAMPLE_LEVELS = 4, 8192, 65536, 8, 65536
+
+
+def _two_sample_square(who, name, t, dtype):
+    """The limits of an [n, n] argument of the two-sample launchers, by name and before anything touches the device; the
+    shared checks (_dense_rows) then see to device, dtype and layout."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{who}: {name}: expected a CUDA(HIP) tensor")
+    if t.dtype != dtype:
+        raise TypeError(f"{who}: {name}: expected {dtype}, got {t.dtype}")
+    if t.dim() != 2 or t.shape[0] != t.shape[1]:
+        raise ValueError(f"{who}: {name}: expected a square [n, n] matrix, got {tuple(t.shape)}")
+    if not TWO_SAMPLE_MIN_N <= t.shape[0] <= TWO_SAMPLE_MAX_N:
+        raise ValueError(f"{who}: {name}: unsupported shape {tuple(t.shape)} ({TWO_SAMPLE_MIN_N} <= n <= {TWO_SAMPLE_MAX_N})")
+    return _dense_rows(t, f"{who}: {name}", dtype, square=True)
+
+
+def distance_median(dist, *, out=None):
+    """The exact lower median of the ``M = n (n - 1) / 2`` entries above the diagonal of the fp32 distance matrix ``dist``
+    [n, n] (``pti_distance_median``) -> 0-d fp32 DEVICE tensor: element ``(M - 1) // 2`` in ascending order, selected on the
+    bit patterns by an MSB-first radix select with integer histograms.  No sort, no copy of the triangle.  4 <= n <= 8192.
+    Runs on the current stream, no host sync."""
+    who = "distance_median"
+    dist = _two_sample_square(who, "dist", dist, F32)
+    n = dist.shape[0]
+    out = _out(out, (), F32, dist.device, f"{who}: out")
+    stream = _stream()
+    ws, nbytes = _scratch_bytes(who, "ts_median", (n,), L.lib().pti_distance_median_ws_bytes(n), tuple(dist.shape), dist.device,
+                                stream)
+    L.check(L.lib().pti_distance_median(_ptr(dist), dist.stride(0), n, _ptr(out), _ptr(ws), nbytes, stream), "pti_distance_median")
+    return out
+
+
+def two_sample_kernel(dist, kind, *, scale=None, bandwidths=(0.5, 1.0, 2.0), out=None, scale_out=None):
+    """The 16-bit integer weight matrix of a two-sample test from the fp32 distance matrix ``dist`` [n, n]
+    (``pti_two_sample_kernel``) -> int32 ``[n, n]`` with entries in [0, 65535] and a zero diagonal.
+    ``kind="gaussian"``: ``rint(65535 mean_b exp(-d^2 / (2 (b scale)^2)))`` over ``bandwidths``, ``scale`` a one-element fp32
+    device tensor (``distance_median``'s result).  ``kind="energy"``: ``rint(65535 d / scale)``, ``scale`` the matrix maximum
+    (found on the device) unless one is given.  The expression is evaluated in fp64 and rounded once; a scale that is not
+    positive gives an all-zero matrix.  ``scale_out``: a one-element fp32 device tensor that receives the scale used.
+    4 <= n <= 8192, 1 .. 8 positive bandwidths.  Runs on the current stream, no host sync."""
+    who = "two_sample_kernel"
+    if kind not in ("gaussian", "energy"):
+        raise ValueError(f"{who}: kind must be 'gaussian' or 'energy', got {kind!r}")
+    bw = [float(b) for b in bandwidths]
+    if not 1 <= len(bw) <= TWO_SAMPLE_MAX_BANDWIDTHS or not all(0.0 < b < math.inf for b in bw):
+        raise ValueError(f"{who}: bandwidths must be 1 .. {TWO_SAMPLE_MAX_BANDWIDTHS} positive finite values, got {bandwidths!r}")
+    if kind == "gaussian" and scale is None:
+        raise ValueError(f"{who}: scale: the gaussian kind needs one (distance_median's result)")
+    dist = _two_sample_square(who, "dist", dist, F32)
+    n = dist.shape[0]
+    if scale is not None:
+        _tensor(scale, F32, f"{who}: scale")
+        if scale.numel() != 1 or scale.device != dist.device:
+            raise ValueError(f"{who}: scale must hold one float on {dist.device}")
+    out = _out(out, (n, n), I32, dist.device, f"{who}: out")
+    if scale_out is None:
+        scale_out = torch.empty((), dtype=F32, device=dist.device)
+    else:
+        _tensor(scale_out, F32, f"{who}: scale_out")
+        if scale_out.numel() != 1 or scale_out.device != dist.device:
+            raise ValueError(f"{who}: scale_out must hold one float on {dist.device}")
+    arr = (C.c_double * len(bw))(*bw)
+    L.check(L.lib().pti_two_sample_kernel(_ptr(dist), dist.stride(0), n, int(kind == "energy"), _ptr(scale), arr, len(bw),
+                                          _ptr(out), _ptr(scale_out), _stream()), "pti_two_sample_kernel")
+    return out
+
+
+def knn_indicator(knn_idx, n, *, out=None):
+    """The 0/1 neighbour matrix of ``umap_knn``'s index table (``pti_knn_indicator``): ``knn_idx`` int32 [n, k] -> int32
+    ``[n, n]`` with ``out[i, j] = 1`` where ``j`` is listed in row ``i`` and ``j != i``.  Asymmetric by nature.
+    4 <= n <= 8192, 1 <= k <= n.  Runs on the current stream, no host sync."""
+    who = "knn_indicator"
+    if not isinstance(knn_idx, torch.Tensor):
+        raise ValueError(f"{who}: knn_idx: expected a CUDA(HIP) tensor")
+    if knn_idx.dtype != I32:
+        raise TypeError(f"{who}: knn_idx: expected {I32}, got {knn_idx.dtype}")
+    n = int(n)
+    if not TWO_SAMPLE_MIN_N <= n <= TWO_SAMPLE_MAX_N:
+        raise ValueError(f"{who}: n: unsupported value {n} ({TWO_SAMPLE_MIN_N} <= n <= {TWO_SAMPLE_MAX_N})")
+    if knn_idx.dim() != 2 or knn_idx.shape[0] != n or not 1 <= knn_idx.shape[1] <= n:
+        raise ValueError(f"{who}: knn_idx must be [{n}, k] with 1 <= k <= {n}, got {tuple(knn_idx.shape)}")
+    _tensor(knn_idx, I32, f"{who}: knn_idx", 2)
+    out = _out(out, (n, n), I32, knn_idx.device, f"{who}: out")
+    L.check(L.lib().pti_knn_indicator(_ptr(knn_idx), n, knn_idx.shape[1], _ptr(out), _stream()), "pti_knn_indicator")
+    return out
+
+
+def permutation_forms(w, masks, *, out=None):
+    """The three integer forms of every 0/1 labelling over one integer matrix (``pti_permutation_forms``): ``w`` int32 [n, n]
+    with entries in [0, 65535] (the caller's contract; it need not be symmetric), ``masks`` uint8 [P, n] of 0/1, row 0 by
+    convention the observed labelling -> int64 ``[P, 3]`` = ``(s^T W s, s . (W 1), s . (W^T 1))`` per row ``s``.  ``w`` is
+    split into two int8 byte planes and ``S . plane`` runs on the int8 MFMA with i32 accumulators; everything is combined in
+    64-bit integers: every output integer is exact, independent of tiling and launch order, bitwise reproducible.
+    4 <= n <= 8192, 1 <= P <= 65536.  The scratch buffer is cached per (stream, shape).  Runs on the current stream, no
+    host sync."""
+    who = "permutation_forms"
+    w = _two_sample_square(who, "w", w, I32)
+    n = w.shape[0]
+    if not isinstance(masks, torch.Tensor):
+        raise ValueError(f"{who}: masks: expected a CUDA(HIP) tensor")
+    if masks.dtype != torch.uint8:
+        raise TypeError(f"{who}: masks: expected {torch.uint8}, got {masks.dtype}")
+    if masks.dim() != 2 or masks.shape[1] != n:
+        raise ValueError(f"{who}: masks must be [P, {n}] (one column per row of w), got {tuple(masks.shape)}")
+    p = masks.shape[0]
+    if not 1 <= p <= TWO_SAMPLE_MAX_P:
+        raise ValueError(f"{who}: masks: unsupported number of labellings {p} (1 <= P <= {TWO_SAMPLE_MAX_P})")
+    _tensor(masks, torch.uint8, f"{who}: masks", 2)
+    if masks.device != w.device:
+        raise ValueError(f"{who}: masks must be on {w.device}")
+    out = _out(out, (p, 3), I64, w.device, f"{who}: out")
+    stream = _stream()
+    ws, nbytes = _scratch_bytes(who, "ts_forms", (n, p), L.lib().pti_permutation_forms_ws_bytes(n, p), (tuple(w.shape), p),
+                                w.device, stream)
+    L.check(L.lib().pti_permutation_forms(_ptr(w), w.stride(0), n, _ptr(masks), p, _ptr(out), _ptr(ws), nbytes, stream),
+            "pti_permutation_forms")
+    return out
